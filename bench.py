@@ -13,6 +13,10 @@ N > 1: one process per GPU (torch.distributed, nccl = RCCL).  Ranks take disjoin
 scaling, no collective in the data path); after each step the compressed block stream is gathered to
 rank 0 in archive order (dsrc_amd/dist.py), inside the timed region and overlapped with the next step's compression
 (two output buffers per scheduler instance).
+
+A plain run sets up, warms up, times the K steps and prints the line.  --full adds everything else: the parity checks against
+the oracle (--check), the decompression line, the CPU baseline, the verify / queue-form / one-handle / four-level / CLI lines and,
+with N > 1, the checked gather of the last step.  --dump-outputs DIR writes what the last timed step returned (dump_outputs).
 """
 from __future__ import annotations
 
@@ -35,6 +39,8 @@ RECS_PER_BLOCK = 22300
 PMC_FILE = os.path.join(ROOT, "profiles", "r06_pmc_final.json")   # written by tools/r06_pmc.sh from rocprofv3 --pmc passes of the library it names
 MAX_RESIDENT = 3                  # distinct input shards kept in HBM per scheduler instance (2 when N > 1: rank 0 also holds the gathered streams)
 MAX_RESIDENT_BOX = [MAX_RESIDENT]   # ... lowered by main() when the device has less free HBM than the run would take
+DUMP_BYTES = 8 << 20              # --dump-outputs: block bytes written (as float32: 32 MB), besides the per-block tables
+DUMP_SEED = 0
 
 
 def csrc_sha() -> str:
@@ -61,12 +67,12 @@ def load_pmc():
     return pmc, f"{os.path.relpath(PMC_FILE, ROOT)} (commit {pmc.get('commit')})"
 
 
+POW10 = 10 ** np.arange(1, 19, dtype=np.int64)
+
+
 def title_len(i: np.ndarray) -> np.ndarray:
     def digits(v):
-        d = np.ones(v.shape, dtype=np.int64)
-        for k in range(1, 19):
-            d += (v >= 10 ** k)
-        return d
+        return 1 + np.searchsorted(POW10, v, side="right")          # 1 + #{k >= 1: 10^k <= v}
     x = 1000 + (7 * i) % 20000
     y = 2000 + (13 * i) % 90000
     return 8 + digits(i) + 26 + 1 + 1 + 4 + 1 + digits(x) + 1 + digits(y) + 13
@@ -580,6 +586,35 @@ def measure_host_e2e(src, size, td, inst=4, runs=3, gap=15.0, first_gap=15.0):
             "note": "dsrc-amd c -d3 -q2 / dsrc-amd d on BASELINE configs[2]'s own file (100 M reads), file in tmpfs to file in tmpfs, process start to exit, PCIe and file I/O included; runs separated by %.0f s (%.0f s before the first)" % (gap, first_gap)}
 
 
+def dump_outputs(path, lanes, step):
+    """--dump-outputs: what the callers of the timed path received from their dsrcgpu_compress_batch_device calls of step `step`,
+    scheduler instance after instance (one call each): per block its offset in the instance's output buffer, its size, and the raw
+    and compressed sizes of its four streams -- all of them -- and of the block bytes a fixed sample: whole blocks in an order drawn
+    with DUMP_SEED until DUMP_BYTES (the last one cut short).  Every array is float64 but the bytes (float32)."""
+    os.makedirs(path, exist_ok=True)
+    offs, sizes, raw, comp, where = [], [], [], [], []
+    for ln in lanes:
+        o_offs, o_sizes, o_raw, o_comp = ln.results[step]
+        d_out = ln.outs[step % len(ln.outs)][0]
+        offs += o_offs; sizes += o_sizes; raw += o_raw; comp += o_comp
+        where += [(ln.h, d_out + o) for o in o_offs]
+    n = len(sizes)
+    picked, pieces, left = [], [], DUMP_BYTES
+    for i in np.random.default_rng(DUMP_SEED).permutation(n):
+        if left <= 0:
+            break
+        h, ptr = where[i]
+        take = min(sizes[i], left)
+        pieces.append(np.frombuffer(h.dev_download(ptr, take), dtype=np.uint8))
+        picked.append(i); left -= take
+    arrays = {"block_offsets": np.asarray(offs, dtype=np.float64), "block_sizes": np.asarray(sizes, dtype=np.float64),
+              "raw_sizes": np.asarray(raw, dtype=np.float64).reshape(n, 4), "comp_sizes": np.asarray(comp, dtype=np.float64).reshape(n, 4),
+              "sample_blocks": np.asarray(picked, dtype=np.float64),
+              "sample_bytes": np.concatenate(pieces).astype(np.float32) if pieces else np.zeros(0, dtype=np.float32)}
+    for name, a in arrays.items():
+        np.save(os.path.join(path, name + ".npy"), a)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -592,11 +627,14 @@ def main():
     ap.add_argument("--buf-mb", type=int, default=8, help="chunk size (the reference's -b; 8 = BASELINE's configurations; -m1 / -m2 of the reference's command line are 64 / 256)")
     ap.add_argument("--dna", type=int, default=3)
     ap.add_argument("--qua", type=int, default=2)
-    ap.add_argument("--no-cpu", action="store_true")
+    ap.add_argument("--full", action="store_true", help="after the headline: the parity checks, the secondary lines (decompression, CPU baseline, verify, queue form, "
+                    "one handle, four-level qualities, CLI end to end) and, with N > 1, the checked gather; without it only the headline is measured")
+    ap.add_argument("--no-cpu", action="store_true", help="--full: no CPU baseline, nor the lines that follow it")
     ap.add_argument("--cpu-blocks", type=int, default=int(os.environ.get("DSRC_BENCH_CPU_BLOCKS", "480")), help="8 MiB chunks of the CPU baseline sample (480 = 4 GB)")
     ap.add_argument("--decode-blocks", type=int, default=int(os.environ.get("DSRC_BENCH_DECODE_BLOCKS", "3600")),
-                    help="blocks of the secondary decompression measurement (0 = skip)")
-    ap.add_argument("--check", type=int, default=2, help="blocks of the first sub-batch to verify against the oracle")
+                    help="--full: blocks of the secondary decompression measurement (0 = skip)")
+    ap.add_argument("--check", type=int, default=2, help="--full: blocks of the first sub-batch to verify against the oracle")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR", help="write what the last timed step returned into DIR as .npy files (dump_outputs)")
     ap.add_argument("--dump-step", default=None, help="N > 1 code path only (tests): rank 0 writes the gathered block stream of the last step as an archive (gathered.dsrc) and the FASTQ text of that step (step.fastq) into this directory")
     args = ap.parse_args()
     global BUF, RECS_PER_BLOCK
@@ -715,7 +753,7 @@ def main():
     for s in range(args.warmup):
         for ln in lanes:
             res = ln.run(s); t_sub = ln.timing[-1][0] / 1e3        # GPU time of one sub-batch (HIP events), excludes arena allocation
-            if first_chunks is None and args.check and rank == 0:
+            if first_chunks is None and args.full and args.check and rank == 0:
                 d_in, starts, sizes = ln.shard(s)
                 n = min(args.check, sub_blocks)
                 first_chunks = [ln.h.dev_download(d_in + starts[i], sizes[i]) for i in range(n)]
@@ -787,6 +825,8 @@ def main():
         for s in range(args.warmup, total_steps):
             in_bytes += sum(ln.shard(s)[2]) + len(ln.shard(s)[2])
             out_bytes += sum(ln.results[s][1])
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, lanes, total_steps - 1)
 
     # parity spot-check against the oracle (outside the timed region)
     checked = 0
@@ -800,7 +840,7 @@ def main():
             checked += 1
     # ... and of what the timed region itself produced while all scheduler instances were running concurrently:
     # the last block of every instance's final sub-batch (still in its output buffer)
-    if rank == 0 and args.check:
+    if rank == 0 and args.full and args.check:
         from tests._oracle import Oracle
         o = Oracle()
         last = total_steps - 1
@@ -814,7 +854,7 @@ def main():
             checked += 1
 
     per_rank = None; gather_verified = None
-    if dist is not None:
+    if dist is not None and (args.full or args.dump_step):
         # ---- one more gather of the last step, checked (outside the timed region): the footer table rank 0 assembled is every rank's
         # own list of block sizes, and the bytes rank 0 holds for rank r have the checksum rank r computed of its own buffer
         last = total_steps - 1
@@ -860,6 +900,7 @@ def main():
                     for ln in lanes:
                         d_in, starts, szs = ln.shard(last)
                         f.write(ln.h.dev_download(d_in + starts[0], starts[-1] + szs[-1] + 1 - starts[0]))
+    if dist is not None:
         t = torch.tensor([wall, float(in_bytes), float(out_bytes)], device=xdev, dtype=torch.float64)
         allt = [torch.zeros_like(t) for _ in range(world)]
         dist.all_gather(allt, t)
@@ -919,11 +960,11 @@ def main():
                 "model_traffic": int(pc["model_bytes_per_block"] * sub_blocks) if pc else None,
                 "note": "traffic = FETCH_SIZE x 2 + WRITE_SIZE of the k_part launches of a 512-block batch / 512; model_ms / model_traffic = k_binoff + k_model (adaptive counter rows in LDS, one wave per bucket) + k_place (time bins into stream order) of the same sub-batch"}
         decode_line = None
-        if args.decode_blocks > 0 and world == 1:
+        if args.full and args.decode_blocks > 0 and world == 1:
             decode_line = measure_decode(lanes, cfg, args.decode_blocks, total_steps - 1, pmc)
             if decode_line:
                 line["decompress"] = decode_line
-        if not args.no_cpu and world == 1:
+        if args.full and not args.no_cpu and world == 1:
             ln = lanes[0]
             need = max(1, args.cpu_blocks)
 

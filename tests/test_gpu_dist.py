@@ -34,7 +34,7 @@ def test_bench_dist_path_gathers_the_cli_archive(tmp_path):
     env = dict(os.environ, DSRC_BENCH_FORCE_DIST="1", RANK="0", WORLD_SIZE="1", LOCAL_RANK="0", MASTER_ADDR="127.0.0.1",
                MASTER_PORT=str(_free_port()), HSA_ENABLE_IPC_MODE_LEGACY="0")
     out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--pipeline", "1", "--blocks", "6", "--steps", "1", "--warmup", "0",
-                          "--no-cpu", "--decode-blocks", "0", "--check", "0", "--dump-step", str(tmp_path)], env=env, cwd=ROOT, capture_output=True, text=True, timeout=550)
+                          "--full", "--no-cpu", "--decode-blocks", "0", "--check", "0", "--dump-step", str(tmp_path)], env=env, cwd=ROOT, capture_output=True, text=True, timeout=550)
     assert out.returncode == 0, out.stderr[-2000:]
     line = json.loads([x for x in out.stdout.splitlines() if x.startswith("{")][-1])
     assert line["config"]["gather_verified"] is True
@@ -46,7 +46,7 @@ def test_bench_dist_path_gathers_the_cli_archive(tmp_path):
     # rank 0's table and every rank's digest of its own stream are checked after the timed region
     env["MASTER_PORT"] = str(_free_port())
     out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--pipeline", "2", "--blocks", "8", "--steps", "2", "--warmup", "1",
-                          "--no-cpu", "--decode-blocks", "0", "--check", "1"], env=env, cwd=ROOT, capture_output=True, text=True, timeout=550)
+                          "--full", "--no-cpu", "--decode-blocks", "0", "--check", "1"], env=env, cwd=ROOT, capture_output=True, text=True, timeout=550)
     assert out.returncode == 0, out.stderr[-2000:]
     line = json.loads([x for x in out.stdout.splitlines() if x.startswith("{")][-1])
     assert line["config"]["gather_verified"] is True and line["steps"] == 2 and "1 ranks in the RCCL group" in line["config"]["parallelism"]
@@ -60,7 +60,7 @@ def test_bench_gpus_2_starts_its_own_ranks():
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT", "DSRC_BENCH_FORCE_DIST")}
     env["DSRC_BENCH_SAME_GPU"] = "1"
     out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--pipeline", "2", "--blocks", "8", "--steps", "2", "--warmup", "1",
-                          "--no-cpu", "--decode-blocks", "0", "--check", "1"], env=env, cwd=ROOT, capture_output=True, text=True, timeout=850)
+                          "--full", "--no-cpu", "--decode-blocks", "0", "--check", "1"], env=env, cwd=ROOT, capture_output=True, text=True, timeout=850)
     assert out.returncode == 0, out.stderr[-3000:]
     lines = [x for x in out.stdout.splitlines() if x.startswith("{")]
     assert len(lines) == 1, "rank 0 alone prints the line"

@@ -6,10 +6,10 @@ export TMPDIR=/tmp
 O=gpurun_out/profiles; mkdir -p $O
 bash tools/r06_profiles.sh > $O/r06_profiles.log 2>&1
 bash tools/r06_pmc.sh > $O/r06_pmc.log 2>&1
-( time python bench.py ) > $O/r06_bench_default.json 2> $O/r06_bench_default.err
+( time python bench.py --full ) > $O/r06_bench_default.json 2> $O/r06_bench_default.err
 {
   export DSRC_BENCH_NO_FORMS=1
-  run() { echo "== $*"; timeout 900 python bench.py --no-cpu --decode-blocks 0 --check 1 "$@" 2>/dev/null | tail -1 | python3 -c "
+  run() { echo "== $*"; timeout 900 python bench.py --full --no-cpu --decode-blocks 0 --check 1 "$@" 2>/dev/null | tail -1 | python3 -c "
 import json,sys
 l=json.loads(sys.stdin.readline()); r=l['roofline']; print(l['value'], 'MB/s  ms_per_step', l['ms_per_step'], ' k_rcs ms', r['kernel_ms'], ' batch_ms', r['batch_ms'], ' hbm GB', l['config'].get('hbm_held_GB'))"; }
   run --buf-mb 64 --blocks 224 --pipeline 4 --steps 3 --warmup 1

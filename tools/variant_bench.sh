@@ -9,7 +9,7 @@ for v in "$@"; do
 	lib=$PWD/dsrc_amd/csrc/_var/lib_$v.so
 	[ -f "$lib" ] || { echo "$v: no such build" >> $out; continue; }
 	echo "== $v p1" >> $out
-	DSRC_GPU_LIB=$lib timeout 300 python bench.py --pipeline 1 --blocks 512 --steps 3 --no-cpu --decode-blocks 0 --check ${VB_CHECK:-2} 2>&1 | tail -1 | python -c '
+	DSRC_GPU_LIB=$lib timeout 300 python bench.py --full --pipeline 1 --blocks 512 --steps 3 --no-cpu --decode-blocks 0 --check ${VB_CHECK:-2} 2>&1 | tail -1 | python -c '
 import sys, json
 try:
     r = json.loads(sys.stdin.read())
