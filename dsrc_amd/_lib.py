@@ -27,6 +27,12 @@ EXPORTS = [
 ]
 
 
+# flavours of dsrcgpu_synth_fastq (include/dsrc_gpu.h)
+SYNTH_ILLUMINA = 0
+SYNTH_ILLUMINA_BINNED = 1
+SYNTH_IONTORRENT = 2
+
+
 class Settings(C.Structure):
     _fields_ = [("dna_order", C.c_uint32), ("quality_order", C.c_uint32), ("tag_preserve_flags", C.c_uint64),
                 ("lossy", C.c_uint8), ("calculate_crc32", C.c_uint8), ("verify_after_compress", C.c_uint8),
@@ -307,4 +313,10 @@ class Handle:
     def synth_illumina(self, first: int, count: int, d_out: int, cap: int, binned: bool = False) -> int:
         n = C.c_uint64()
         self._chk(self.L.dsrcgpu_synth_fastq(self.h, C.c_uint32(1 if binned else 0), C.c_uint64(first), C.c_uint64(count), C.c_void_p(d_out), C.c_uint64(cap), C.byref(n)))
+        return n.value
+
+    def synth_fastq(self, flavour: int, first: int, count: int, d_out: int, cap: int) -> int:
+        """Records first..first+count-1 of a SYNTH_* flavour written to d_out; returns the byte count (dsrc_amd/synth.py has the same bytes)."""
+        n = C.c_uint64()
+        self._chk(self.L.dsrcgpu_synth_fastq(self.h, C.c_uint32(flavour), C.c_uint64(first), C.c_uint64(count), C.c_void_p(d_out), C.c_uint64(cap), C.byref(n)))
         return n.value

@@ -2417,8 +2417,14 @@ int dsrcgpu_synth_fastq(dsrcgpu_handle* h, uint32_t flavour, uint64_t first, uin
 {
 	if (!h) return DSRCGPU_E_ARG;
 	if (!d_out || !bytes) return fail(h, DSRCGPU_E_ARG, "null argument");
-	if (flavour > 1) return fail(h, DSRCGPU_E_ARG, "unknown synthetic flavour %u", flavour);
+	if (flavour > 2) return fail(h, DSRCGPU_E_ARG, "unknown synthetic flavour %u", flavour);
 	HIPCHK(hipSetDevice(h->device));
+	if (flavour == 2)
+	{
+		const int rc = synth_iontorrent_device(h->stream, first, count, (u8*)d_out, cap, bytes);
+		if (rc == 2) return fail(h, DSRCGPU_E_NOMEM, "synthetic FASTQ: no device memory for the group totals");
+		return rc ? fail(h, DSRCGPU_E_CAPACITY, "synthetic FASTQ does not fit in %llu bytes", (unsigned long long)cap) : DSRCGPU_OK;
+	}
 	return synth_illumina_device(h->stream, first, count, (u8*)d_out, cap, bytes, flavour) ? fail(h, DSRCGPU_E_CAPACITY, "synthetic FASTQ does not fit in %llu bytes", (unsigned long long)cap) : DSRCGPU_OK;
 }
 

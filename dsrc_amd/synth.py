@@ -78,6 +78,21 @@ def illumina_fastq(n_reads: int, first: int = 1, read_len: int = 150, seed: int 
 _IUPAC = np.frombuffer(b"NRYKMSWBDHV", dtype=np.uint8)
 
 
+_POW10 = 10 ** np.arange(1, 20, dtype=np.uint64)
+
+
+def iontorrent_record_sizes(first: int, count: int, seed: int = SEED ^ 0x454) -> np.ndarray:
+    """Byte size of each record of iontorrent_fastq(count, first), newlines included, without generating them:
+    np.cumsum of it gives the record offsets of the device generator's output (flavour 2 of dsrcgpu_synth_fastq)."""
+    i = np.arange(first, first + count, dtype=np.uint64)
+    with np.errstate(over="ignore"):
+        L = np.uint64(40) + _mix64((i << np.uint64(10)) ^ np.uint64(seed) ^ np.uint64(0xABCDEF)) % np.uint64(461)
+    L = L.astype(np.int64)
+    id_digits = 1 + np.searchsorted(_POW10, i, side="right")
+    # "@GXYZ1234." id " length=" L " xy=" 4 "_" 4 " region=" 1, then title, sequence, '+' and quality newlines
+    return 10 + id_digits + 8 + np.where(L >= 100, 3, 2) + 4 + 4 + 1 + 4 + 8 + 1 + 2 * L + 5
+
+
 def iontorrent_fastq(n_reads: int, first: int = 1, seed: int = SEED ^ 0x454) -> bytes:
     """Config 5 shape: 454/Ion-Torrent-like variable-length reads (40..500) with 1 % IUPAC codes."""
     out = []

@@ -245,7 +245,11 @@ int dsrcgpu_last_stage_timing(const dsrcgpu_handle* h, float* sort_ms, float* re
  * dsrc_amd/synth.py illumina_fastq).  Writes records first..first+count-1, returns the byte count. */
 int dsrcgpu_synth_illumina(dsrcgpu_handle* h, uint64_t first, uint64_t count, void* d_out, uint64_t cap, uint64_t* bytes);
 /* ... with a flavour: 0 = the generator above (BASELINE's configurations); 1 = the same records with the qualities quantised to four
- * levels (Phred 2 / 12 / 23 / 37: what current instruments write) -- dsrc_amd/synth.py illumina_fastq(binned=True); bench.py's second line. */
+ * levels (Phred 2 / 12 / 23 / 37: what current instruments write) -- dsrc_amd/synth.py illumina_fastq(binned=True); bench.py's second line;
+ * 2 = variable-length 454/Ion-Torrent-like reads (40..500 bases, 1 % IUPAC codes, zero qualities under most of them), the same bytes as
+ * dsrc_amd/synth.py iontorrent_fastq: the input of BASELINE's configuration 5 (-d2 -q1, lossy), timed by tools/config_bench.py.
+ * Any other flavour: DSRCGPU_E_ARG.  count == 0: *bytes = 0.  Output larger than cap: DSRCGPU_E_CAPACITY, *bytes = the size needed,
+ * nothing written. */
 int dsrcgpu_synth_fastq(dsrcgpu_handle* h, uint32_t flavour, uint64_t first, uint64_t count, void* d_out, uint64_t cap, uint64_t* bytes);
 
 /* small HBM helpers so that non-HIP hosts (Python/ctypes, JNI ...) can stage device-resident batches */
