@@ -10,6 +10,7 @@ from __future__ import annotations
 
 import ctypes as C
 import os
+import typing
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 DEFAULT_LIB = os.path.join(HERE, "csrc", "libdsrc_gpu.so")
@@ -24,7 +25,13 @@ EXPORTS = [
     "dsrcgpu_title_fields", "dsrcgpu_fields_capacity_after", "dsrcgpu_set_fields_capacity", "dsrcgpu_get_fields_capacity",
     "dsrcgpu_chain_seed", "dsrcgpu_last_stage_timing", "dsrcgpu_try_collect", "dsrcgpu_prepare", "dsrcgpu_set_table_budget", "dsrcgpu_device_memory", "dsrcgpu_release_memory",
     "dsrcgpu_synth_fastq", "dsrcgpu_reserve_memory", "dsrcgpu_set_lanes", "dsrcgpu_submit_pinned",
+    "dsrcgpu_decompress_batch_columns_device",
 ]
+
+# error codes of include/dsrc_gpu.h that callers tell apart (DsrcGpuError.code)
+E_ARG = -1
+E_CAPACITY = -4
+E_INPUT = -5
 
 
 # flavours of dsrcgpu_synth_fastq (include/dsrc_gpu.h)
@@ -42,6 +49,25 @@ class Settings(C.Structure):
 class Dataset(C.Structure):
     _fields_ = [("quality_offset", C.c_uint32), ("plus_repetition", C.c_uint8), ("color_space", C.c_uint8),
                 ("reserved", C.c_uint8 * 2)]
+
+
+class Columns(C.Structure):
+    """dsrcgpu_columns: the caller's device arrays of dsrcgpu_decompress_batch_columns_device."""
+    _fields_ = [("d_bases", C.c_void_p), ("bases_cap", C.c_uint64), ("d_quals", C.c_void_p), ("quals_cap", C.c_uint64),
+                ("d_titles", C.c_void_p), ("titles_cap", C.c_uint64), ("d_seq_offs", C.c_void_p), ("d_title_offs", C.c_void_p),
+                ("records_cap", C.c_uint64)]
+
+
+class HostColumns(typing.NamedTuple):
+    """What Handle.decompress_columns returns: the five arrays as numpy (titles / title_offsets None when not wanted)."""
+    bases: object
+    quals: object
+    titles: object
+    seq_offsets: object
+    title_offsets: object
+    block_records: list
+    totals: list
+    crc_ok: object
 
 
 class DsrcGpuError(RuntimeError):
@@ -230,6 +256,63 @@ class Handle:
         self._chk(self.L.dsrcgpu_decompress_batch_device(self.h, n, C.c_void_p(d_in), a_offs, a_sizes, None, C.c_void_p(d_out),
                                                          C.c_uint64(out_cap), o_offs, o_sizes, ok if verify else None))
         return (list(o_offs), list(o_sizes), list(ok)) if verify else (list(o_offs), list(o_sizes))
+
+    def decompress_columns_device(self, d_in: int, offs, sizes, cols: Columns, text_caps=None, verify=False):
+        """dsrcgpu_decompress_batch_columns_device: the records of the blocks as arrays in the caller's device memory (`cols`).
+        Returns (block_records, totals[, crc_ok]); DsrcGpuError.code == E_CAPACITY when an array is too small -- `need` of the
+        exception then holds the totals (records, bases, title bytes) to allocate for."""
+        n = len(offs)
+        a_offs = (C.c_uint64 * max(n, 1))(*offs); a_sizes = (C.c_uint64 * max(n, 1))(*sizes)
+        caps = (C.c_uint64 * n)(*text_caps) if text_caps else None
+        recs = (C.c_uint64 * (n + 1))(); totals = (C.c_uint64 * 3)(); ok = (C.c_uint32 * max(n, 1))()
+        rc = self.L.dsrcgpu_decompress_batch_columns_device(self.h, C.c_uint32(n), C.c_void_p(d_in), a_offs, a_sizes, caps, C.byref(cols),
+                                                            recs, totals, ok if verify else None)
+        if rc < 0:
+            e = DsrcGpuError(rc, self.L.dsrcgpu_last_error(self.h).decode())
+            e.need = list(totals) if rc == E_CAPACITY else None
+            raise e
+        return (list(recs), list(totals), list(ok)[:n]) if verify else (list(recs), list(totals))
+
+    def decompress_columns(self, blocks, titles=True, text_caps=None, verify=False) -> HostColumns:
+        """Host convenience over decompress_columns_device: stages the blocks in HBM, sizes the arrays from a first call with
+        capacities of zero, decodes, and brings the arrays back as numpy."""
+        import numpy as np
+        n = len(blocks)
+        offs, pos = [], 0
+        for b in blocks:
+            offs.append(pos); pos += (len(b) + 63) // 64 * 64
+        sizes = [len(b) for b in blocks]
+        held = []
+
+        def alloc(nbytes):
+            p = self.dev_alloc(max(nbytes, 8)); held.append(p)
+            return p
+
+        def fetch(ptr, count, dtype):
+            nbytes = count * np.dtype(dtype).itemsize
+            return np.frombuffer(self.dev_download(ptr, nbytes), dtype=dtype).copy() if nbytes else np.zeros(0, dtype)
+        try:
+            d_in = alloc(pos)
+            for b, o in zip(blocks, offs):
+                self.dev_upload(d_in + o, b)
+            need = [0, 0, 0]
+            if n:
+                try:
+                    self.decompress_columns_device(d_in, offs, sizes, Columns(), text_caps=text_caps)
+                except DsrcGpuError as e:
+                    if e.code != E_CAPACITY or not any(e.need):      # (all zero: it is a block's TEXT that does not fit its text_caps)
+                        raise
+                    need = e.need
+            R, S, T = need
+            cols = Columns(alloc(S), S, alloc(S), S, alloc(T) if titles else None, T if titles else 0,
+                           alloc(8 * (R + 1)), alloc(8 * (R + 1)) if titles else None, R)
+            res = self.decompress_columns_device(d_in, offs, sizes, cols, text_caps=text_caps, verify=verify)
+            return HostColumns(fetch(cols.d_bases, S, np.uint8), fetch(cols.d_quals, S, np.uint8),
+                               fetch(cols.d_titles, T, np.uint8) if titles else None, fetch(cols.d_seq_offs, R + 1, np.uint64),
+                               fetch(cols.d_title_offs, R + 1, np.uint64) if titles else None, res[0], res[1], res[2] if verify else None)
+        finally:
+            for p in held:
+                self.dev_free(p)
 
     def compress_batch_device(self, d_in: int, offs, sizes, d_out: int, out_cap: int):
         n = len(offs)

@@ -44,6 +44,7 @@
 #include "k_dec_rc.h"
 #include "k_dec_tags.h"
 #include "k_dec_q0.h"
+#include "k_columns.h"
 
 namespace
 {
@@ -1179,6 +1180,8 @@ struct DecodeIO
 	u64* out_offs; u64* out_sizes;
 	u32* crc_ok;                     // optional, per block: 1 = the stored checksums match the decoded records
 	const DecHint* hints = nullptr;  // optional (verification of blocks just written): start and length of every block's DNA stream
+	const dsrcgpu_columns* cols = nullptr;       // optional: the records as arrays as well (k_columns.h); the caller's device arrays
+	u64* col_block_records = nullptr; u64* col_totals = nullptr;      // ... and its two host outputs: n + 1 entries, 3 entries
 };
 
 // ---- model tables of the range-decoded levels (here DENSE: every row is reachable) ------------------------
@@ -1332,6 +1335,9 @@ int run_decode(dsrcgpu_handle* h, DecodeIO io)
 	rp.kept = AP<u16>(h, A.alloc(recs * 2)); rp.trunc = nullptr;
 	rp.q_off = nullptr; rp.d_off = AP<u32>(h, A.alloc(recs * 4));
 	const size_t o_d = A.alloc(dbytes + 64), o_nodes = A.alloc(nodes * 4 + 64), o_fld = A.alloc(fbytes + 64);
+	// columns: block-local prefixes of the read and title lengths (indexed like the pools), the block totals, the blocks' bases
+	size_t o_cseq = 0, o_ctitle = 0, o_ctot = 0, o_cbase = 0;
+	if (io.cols) { o_cseq = A.alloc(recs * 4); o_ctitle = A.alloc(recs * 4); o_ctot = A.alloc(sizeof(u64) * 2 * B); o_cbase = A.alloc(sizeof(ColBase) * B); }
 	u8* d_out = io.d_out;
 	size_t o_out = 0;
 	if (!d_out) o_out = A.alloc(text_total + 64);
@@ -1513,6 +1519,13 @@ int run_decode(dsrcgpu_handle* h, DecodeIO io)
 		hipLaunchKernelGGL(k_dec_layout, dim3(gx, B), dim3(WG), 0, s, d_desc, d_state, rp, d_out, AP<u8>(h, o_d), prm); KCHK();
 	}
 	if (prm.crc && io.crc_ok) { hipLaunchKernelGGL(k_dec_crc, dim3(B, 3), dim3(WG), 0, s, d_desc, d_state, rp, d_out, h->d_crc_tab, prm); KCHK(); }
+	std::vector<u64> col_tot;
+	if (io.cols)
+	{
+		col_tot.resize(2 * (size_t)B);
+		hipLaunchKernelGGL(k_col_sizes, dim3(B), dim3(WG), 0, s, d_desc, d_state, rp, AP<u32>(h, o_cseq), AP<u32>(h, o_ctitle), AP<u64>(h, o_ctot)); KCHK();
+		HIPCHK(hipMemcpyAsync(col_tot.data(), AP<u64>(h, o_ctot), sizeof(u64) * 2 * B, hipMemcpyDeviceToHost, s));
+	}
 	HIPCHK(hipMemcpyAsync(st.data(), d_state, sizeof(DecState) * B, hipMemcpyDeviceToHost, s));
 	HIPCHK(hipEventRecord(h->ev[1], s));
 	if (trace) { HIPCHK(hipStreamSynchronize(s)); mark("dna+layout"); }
@@ -1523,6 +1536,47 @@ int run_decode(dsrcgpu_handle* h, DecodeIO io)
 	{
 		const int rc = check_blocks(true);
 		if (rc) return rc;
+	}
+	if (io.cols)
+	{	// the scan over the blocks stays on the host (B is at most a few thousand), then the capacities, then the gather
+		const dsrcgpu_columns& c = *io.cols;
+		std::vector<ColBase> cbase(B);
+		u64 n_recs = 0, n_bases = 0, n_title = 0; u32 max_n = 1;
+		// (k_col_sizes counts 0 records for a block whose err is set; here no block has: check_blocks(true) above has returned otherwise.
+		// The two counts must stay the same, or the blocks' bases below are not where the kernel's prefixes belong.)
+		for (u32 b = 0; b < B; ++b)
+		{
+			const u32 nr = std::min(st[b].n_recs, desc[b].rec_cap);
+			cbase[b].rec = n_recs; cbase[b].seq = n_bases; cbase[b].title = n_title;
+			n_recs += nr; n_bases += col_tot[2 * b]; n_title += col_tot[2 * b + 1]; max_n = std::max(max_n, nr);
+		}
+		io.col_totals[0] = n_recs; io.col_totals[1] = n_bases; io.col_totals[2] = n_title;
+		if (n_recs > c.records_cap || n_bases > c.bases_cap || n_bases > c.quals_cap || (c.d_titles && n_title > c.titles_cap))
+			return fail(h, DSRCGPU_E_CAPACITY, "columns need %llu records, %llu bases and %llu title bytes; the caller's capacities are %llu records, %llu / %llu bases and qualities, %llu title bytes",
+			            (unsigned long long)n_recs, (unsigned long long)n_bases, (unsigned long long)n_title, (unsigned long long)c.records_cap,
+			            (unsigned long long)c.bases_cap, (unsigned long long)c.quals_cap, (unsigned long long)c.titles_cap);
+		// a sizing call (no arrays at all) on a batch without records: the answer is the totals of 0, there is nothing to write
+		const bool nothing_to_write = n_recs == 0 && !c.d_seq_offs;
+		if (!nothing_to_write && (!c.d_seq_offs || (c.d_titles && !c.d_title_offs) || (n_bases && (!c.d_bases || !c.d_quals))))
+			return fail(h, DSRCGPU_E_ARG, "columns: null array");
+		for (u32 b = 0; b < B; ++b) io.col_block_records[b] = cbase[b].rec;
+		io.col_block_records[B] = n_recs;
+		if (nothing_to_write) { }
+		else if (n_recs == 0)
+		{	// no record, no wave that writes the closing entries
+			HIPCHK(hipMemsetAsync(c.d_seq_offs, 0, sizeof(u64), s));
+			if (c.d_titles) HIPCHK(hipMemsetAsync(c.d_title_offs, 0, sizeof(u64), s));
+		}
+		else
+		{
+			ColBase* d_cbase = AP<ColBase>(h, o_cbase);
+			HIPCHK(hipMemcpyAsync(d_cbase, cbase.data(), sizeof(ColBase) * B, hipMemcpyHostToDevice, s));
+			const ColOut o{c.d_bases, c.d_quals, c.d_titles, c.d_seq_offs, c.d_title_offs, n_recs, n_bases, n_title};
+			const u32 gx = std::max(1u, std::min(64u, (max_n + 4 * WAVES - 1) / (4 * WAVES)));
+			hipLaunchKernelGGL(k_col_gather, dim3(gx, B), dim3(WG), 0, s, d_desc, d_state, rp, d_out, AP<u32>(h, o_cseq), AP<u32>(h, o_ctitle), d_cbase, o, prm); KCHK();
+		}
+		HIPCHK(hipEventRecord(h->ev[1], s));
+		HIPCHK(hipStreamSynchronize(s));
 	}
 	for (u32 b = 0; b < B; ++b)
 	{
@@ -1956,6 +2010,36 @@ int dsrcgpu_decompress_batch_device(dsrcgpu_handle* h, uint32_t n, const void* d
 	HIPCHK(hipSetDevice(h->device));
 	return with_arena_retry_(h, estimate_decode_arena(h, n, sizes, false), [&]() {
 		DecodeIO io{(const u8*)d_blocks, offs, sizes, n, text_caps, (u8*)d_text, text_cap, nullptr, 0, text_offs, text_sizes, crc_ok};
+		return run_decode(h, io);
+	});
+}
+
+int dsrcgpu_decompress_batch_columns_device(dsrcgpu_handle* h, uint32_t n, const void* d_blocks, const uint64_t* offs, const uint64_t* sizes,
+											const uint64_t* text_caps, const dsrcgpu_columns* out, uint64_t* block_records, uint64_t totals[3], uint32_t* crc_ok)
+{
+	if (!h) return DSRCGPU_E_ARG;
+	if (!out || !block_records || !totals) return fail(h, DSRCGPU_E_ARG, "null argument");
+	if (h->ds.color_space) return fail(h, DSRCGPU_E_ARG, "columns are defined for base space: a colour-space line is a primer plus colours");
+	if (!out->d_titles && out->titles_cap) return fail(h, DSRCGPU_E_ARG, "columns: titles_cap without d_titles");
+	HIPCHK(hipSetDevice(h->device));
+	totals[0] = totals[1] = totals[2] = 0;          // (DSRCGPU_E_CAPACITY with totals of 0: a block's text does not fit its text_caps)
+	if (n == 0)
+	{
+		block_records[0] = 0;
+		if (out->d_seq_offs) HIPCHK(hipMemsetAsync(out->d_seq_offs, 0, sizeof(u64), h->stream));
+		if (out->d_titles && out->d_title_offs) HIPCHK(hipMemsetAsync(out->d_title_offs, 0, sizeof(u64), h->stream));
+		HIPCHK(hipStreamSynchronize(h->stream));
+		return DSRCGPU_OK;
+	}
+	if (!d_blocks || !offs || !sizes) return fail(h, DSRCGPU_E_ARG, "null argument");
+	// the text stays in the arena; + the two prefix arrays (8 bytes a record: records are rarely smaller than that in a block -- a
+	// batch that needs more says so and is run again)
+	size_t in_bytes = 0;
+	for (u32 i = 0; i < n; ++i) in_bytes += (size_t)sizes[i];
+	std::vector<u64> to(n), ts(n);
+	return with_arena_retry_(h, estimate_decode_arena(h, n, sizes, true) + 2 * in_bytes + (size_t)n * 64, [&]() {
+		DecodeIO io{(const u8*)d_blocks, offs, sizes, n, text_caps, nullptr, 0, nullptr, 0, to.data(), ts.data(), crc_ok};
+		io.cols = out; io.col_block_records = block_records; io.col_totals = totals;
 		return run_decode(h, io);
 	});
 }

@@ -129,6 +129,36 @@ int dsrcgpu_decompress_batch_device(dsrcgpu_handle* h, uint32_t n, const void* d
 									const uint64_t* sizes, const uint64_t* text_caps, void* d_text, uint64_t text_cap,
 									uint64_t* text_offs, uint64_t* text_sizes, uint32_t* crc_ok);
 
+/* Columnar decode: the records of the batch as arrays in HBM instead of text (no counterpart in the reference, whose readers get
+ * text and look for the line ends again -- DsrcArchive::ReadNextRecord).  The blocks are decoded exactly as by
+ * dsrcgpu_decompress_batch_device (the text lives in the handle's arena for the duration of the call); two more kernels then
+ * gather bases, qualities and titles of all records, in block order and inside a block in record order, into the caller's arrays:
+ *   d_seq_offs[r] .. d_seq_offs[r + 1]      record r's positions in d_bases and d_quals       (r = 0 .. totals[0] - 1)
+ *   d_title_offs[r] .. d_title_offs[r + 1]  record r's title in d_titles
+ * Offsets are 64-bit and global to the call: d_seq_offs[totals[0]] == totals[1], d_title_offs[totals[0]] == totals[2].
+ * block_records (n + 1 entries, host): exclusive prefix of the records per block; totals (host): records, bases, title bytes.
+ * Any capacity too small: DSRCGPU_E_CAPACITY, totals[] = what is needed, none of the caller's arrays is written (the check is made
+ * on the host before the gathering kernel is launched) -- a call with capacities of 0 is the way to size the arrays.
+ * n == 0: DSRCGPU_OK, totals 0, block_records[0] = 0.  text_caps, crc_ok and block errors: as dsrcgpu_decompress_batch_device.
+ * Base space only: a handle whose dataset has color_space set gets DSRCGPU_E_ARG (a SOLiD line is a primer plus colours, not
+ * bases; there is no column form of it). */
+typedef struct dsrcgpu_columns      /* all pointers are device pointers owned by the caller */
+{
+	uint8_t*  d_bases;       uint64_t bases_cap;    /* one byte per base, records back to back: index of the character in
+	                                                   "ACGTNRWSKMDVHBYXU.-" (A0 C1 G2 T3 N4 ... '-'18); 255 = any other byte */
+	uint8_t*  d_quals;       uint64_t quals_cap;    /* one byte per base, same positions: quality character - quality_offset */
+	uint8_t*  d_titles;      uint64_t titles_cap;   /* title lines back to back as decoded ('@' included, no newline); may be NULL
+	                                                   with titles_cap 0 = titles not wanted, d_title_offs then ignored */
+	uint64_t* d_seq_offs;                           /* records_cap + 1 entries: record r's bases/qualities are [offs[r], offs[r+1]) */
+	uint64_t* d_title_offs;                         /* records_cap + 1 entries */
+	uint64_t  records_cap;
+} dsrcgpu_columns;
+
+int dsrcgpu_decompress_batch_columns_device(dsrcgpu_handle* h, uint32_t n, const void* d_blocks, const uint64_t* offs,
+		const uint64_t* sizes, const uint64_t* text_caps, const dsrcgpu_columns* out,
+		uint64_t* block_records /* n + 1: exclusive prefix of records per block */,
+		uint64_t totals[3]      /* records, bases, title bytes */, uint32_t* crc_ok);
+
 /* Queue form of DsrcCompressor::Process (src/DsrcWorker.cpp:39-70):
  *   fastqQueue.Pop(partId, chunk)            -> dsrcgpu_submit(partId, chunk)      (bytes are copied into page-locked staging)
  *   ... Store ... dsrcQueue.Push(partId, blk) -> dsrcgpu_collect(&partId, &blk, ...)
