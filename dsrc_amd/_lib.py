@@ -25,7 +25,7 @@ EXPORTS = [
     "dsrcgpu_title_fields", "dsrcgpu_fields_capacity_after", "dsrcgpu_set_fields_capacity", "dsrcgpu_get_fields_capacity",
     "dsrcgpu_chain_seed", "dsrcgpu_last_stage_timing", "dsrcgpu_try_collect", "dsrcgpu_prepare", "dsrcgpu_set_table_budget", "dsrcgpu_device_memory", "dsrcgpu_release_memory",
     "dsrcgpu_synth_fastq", "dsrcgpu_reserve_memory", "dsrcgpu_set_lanes", "dsrcgpu_submit_pinned",
-    "dsrcgpu_decompress_batch_columns_device",
+    "dsrcgpu_decompress_batch_columns_device", "dsrcgpu_compress_columns_device", "dsrcgpu_columns_cut",
 ]
 
 # error codes of include/dsrc_gpu.h that callers tell apart (DsrcGpuError.code)
@@ -56,6 +56,12 @@ class Columns(C.Structure):
     _fields_ = [("d_bases", C.c_void_p), ("bases_cap", C.c_uint64), ("d_quals", C.c_void_p), ("quals_cap", C.c_uint64),
                 ("d_titles", C.c_void_p), ("titles_cap", C.c_uint64), ("d_seq_offs", C.c_void_p), ("d_title_offs", C.c_void_p),
                 ("records_cap", C.c_uint64)]
+
+
+class ColumnsIn(C.Structure):
+    """dsrcgpu_columns_in: the caller's device arrays of dsrcgpu_compress_columns_device / dsrcgpu_columns_cut (read only)."""
+    _fields_ = [("d_bases", C.c_void_p), ("bases_len", C.c_uint64), ("d_quals", C.c_void_p), ("d_titles", C.c_void_p),
+                ("titles_len", C.c_uint64), ("d_seq_offs", C.c_void_p), ("d_title_offs", C.c_void_p), ("n_records", C.c_uint64)]
 
 
 class HostColumns(typing.NamedTuple):
@@ -310,6 +316,66 @@ class Handle:
             return HostColumns(fetch(cols.d_bases, S, np.uint8), fetch(cols.d_quals, S, np.uint8),
                                fetch(cols.d_titles, T, np.uint8) if titles else None, fetch(cols.d_seq_offs, R + 1, np.uint64),
                                fetch(cols.d_title_offs, R + 1, np.uint64) if titles else None, res[0], res[1], res[2] if verify else None)
+        finally:
+            for p in held:
+                self.dev_free(p)
+
+    def compress_columns_device(self, cols_in: ColumnsIn, block_records, d_out: int, out_cap: int):
+        """dsrcgpu_compress_columns_device: block i = records block_records[i] .. block_records[i + 1] - 1 of the device arrays
+        `cols_in`, written back to back to d_out.  Returns (block_offs, block_sizes, raw_sizes, comp_sizes)."""
+        n = len(block_records) - 1
+        recs = (C.c_uint64 * (n + 1))(*block_records)
+        o_offs = (C.c_uint64 * max(n, 1))(); o_sizes = (C.c_uint64 * max(n, 1))()
+        raw = (C.c_uint64 * max(4 * n, 1))(); comp = (C.c_uint64 * max(4 * n, 1))()
+        self._chk(self.L.dsrcgpu_compress_columns_device(self.h, C.c_uint32(n), C.byref(cols_in), recs, C.c_void_p(d_out),
+                                                         C.c_uint64(out_cap), o_offs, o_sizes, raw, comp))
+        return list(o_offs)[:n], list(o_sizes)[:n], list(raw)[:4 * n], list(comp)[:4 * n]
+
+    def columns_cut(self, cols_in: ColumnsIn, chunk_bytes: int, cap: int | None = None):
+        """dsrcgpu_columns_cut: the greedy cut of the records of `cols_in` into blocks of at most chunk_bytes of chunk text (at least
+        one record each) -> block_records (blocks + 1 entries).  With `cap` (entries) given, a cut that needs more raises
+        DsrcGpuError with .code == E_CAPACITY and .need = the number of blocks; without, the call is repeated with that many."""
+        grow = cap is None
+        if grow:
+            cap = min(int(cols_in.n_records), 4096) + 1
+        while True:
+            recs = (C.c_uint64 * max(cap, 1))(); n = C.c_uint32()
+            rc = self.L.dsrcgpu_columns_cut(self.h, C.byref(cols_in), C.c_uint64(chunk_bytes), recs, C.c_uint32(cap), C.byref(n))
+            if rc == E_CAPACITY and grow:
+                cap, grow = n.value + 1, False
+                continue
+            if rc < 0:
+                e = DsrcGpuError(rc, self.L.dsrcgpu_last_error(self.h).decode())
+                e.need = n.value if rc == E_CAPACITY else None
+                raise e
+            return list(recs)[: n.value + 1]
+
+    def compress_columns(self, cols, block_records=None, chunk_bytes=8 << 20):
+        """Host convenience over compress_columns_device: `cols` has numpy arrays bases, quals, titles, seq_offsets, title_offsets
+        (a HostColumns, or anything shaped like it); they are staged in HBM, cut with columns_cut unless block_records is given,
+        compressed, and the blocks come back as a list of bytes."""
+        import numpy as np
+        held = []
+
+        def stage(a, dtype):
+            data = np.ascontiguousarray(a, dtype=dtype).tobytes()
+            p = self.dev_alloc(max(len(data), 8)); held.append(p)
+            if data:
+                self.dev_upload(p, data)
+            return p
+        try:
+            R = len(cols.seq_offsets) - 1
+            cin = ColumnsIn(stage(cols.bases, np.uint8), len(cols.bases), stage(cols.quals, np.uint8), stage(cols.titles, np.uint8),
+                            len(cols.titles), stage(cols.seq_offsets, np.uint64), stage(cols.title_offsets, np.uint64), R)
+            if block_records is None:
+                block_records = self.columns_cut(cin, chunk_bytes)
+            block_records = [int(v) for v in block_records]
+            n = len(block_records) - 1
+            # (the text: two bytes a base, the title at most twice, six more a record; a block is not larger than its text + 64 KiB)
+            cap = 2 * len(cols.bases) + 2 * len(cols.titles) + 6 * R + n * (1 << 16) + 64
+            d_out = self.dev_alloc(cap); held.append(d_out)
+            offs, sizes, _, _ = self.compress_columns_device(cin, block_records, d_out, cap)
+            return [self.dev_download(d_out + o, s) for o, s in zip(offs, sizes)]
         finally:
             for p in held:
                 self.dev_free(p)

@@ -1,4 +1,5 @@
-"""Decoded records as torch tensors (dsrcgpu_decompress_batch_columns_device, include/dsrc_gpu.h).
+"""Records as torch tensors: decode_columns (dsrcgpu_decompress_batch_columns_device) and the way back, encode_columns
+(dsrcgpu_compress_columns_device), include/dsrc_gpu.h.
 
 The blocks are already in device memory; the arrays are allocated by torch on the same device and filled by the library's
 kernels -- no text, no host round trip of the payload.  With the emulator build of the library (tests/emu) device pointers
@@ -68,3 +69,35 @@ def decode_columns(handle: _lib.Handle, d_blocks, offs, sizes, device, titles: b
     block_records, totals = handle.decompress_columns_device(d_in, offs, sizes, cols)
     assert totals == need
     return RecordColumns(bases, quals, title_bytes, seq_offsets, title_offsets, torch.tensor(block_records, **i64))
+
+
+def encode_columns(handle: _lib.Handle, cols: RecordColumns, block_records=None, chunk_bytes: int = 8 << 20):
+    """Compress the records of `cols` (tensors on one device, as decode_columns returns them) into DSRC blocks on that device:
+    -> (blocks: uint8 tensor, offs, sizes, block_records); block i is blocks[offs[i] : offs[i] + sizes[i]] and holds records
+    block_records[i] .. block_records[i + 1] - 1.  block_records=None: the greedy cut of dsrcgpu_columns_cut at chunk_bytes of
+    chunk text per block.  No text is written by the caller and nothing of the payload crosses to the host."""
+    device = cols.bases.device
+    R = cols.n_records
+    if cols.title_offsets.numel() != R + 1:
+        raise ValueError("encode_columns needs the titles (decode_columns(..., titles=True))")
+
+    def quiesce():       # as in decode_columns: the library works on its own stream
+        if device.type == "cuda":
+            torch.cuda.current_stream(device).synchronize()
+
+    spare = torch.empty(8, dtype=torch.uint8, device=device)
+    ptr = lambda t: t.data_ptr() if t.numel() else spare.data_ptr()
+    held = [t.contiguous() for t in (cols.bases, cols.quals, cols.titles, cols.seq_offsets, cols.title_offsets)]
+    bases, quals, titles, seq_offs, title_offs = held
+    cin = _lib.ColumnsIn(ptr(bases), bases.numel(), ptr(quals), ptr(titles), titles.numel(), seq_offs.data_ptr(), title_offs.data_ptr(), R)
+    if block_records is None:
+        quiesce()
+        block_records = handle.columns_cut(cin, chunk_bytes)
+    block_records = [int(v) for v in (block_records.tolist() if isinstance(block_records, torch.Tensor) else block_records)]
+    n = len(block_records) - 1
+    # (the text: two bytes a base, the title at most twice, six more a record; a block is not larger than its text + 64 KiB)
+    cap = 2 * bases.numel() + 2 * titles.numel() + 6 * R + n * (1 << 16) + 64
+    blocks = torch.empty(cap, dtype=torch.uint8, device=device)
+    quiesce()
+    offs, sizes, _, _ = handle.compress_columns_device(cin, block_records, blocks.data_ptr(), cap)
+    return blocks, offs, sizes, block_records

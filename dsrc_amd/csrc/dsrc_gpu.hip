@@ -45,6 +45,7 @@
 #include "k_dec_tags.h"
 #include "k_dec_q0.h"
 #include "k_columns.h"
+#include "k_columns_enc.h"
 
 namespace
 {
@@ -181,6 +182,7 @@ struct dsrcgpu_handle
 	float batch_ms = 0.f, rc_ms = 0.f, verify_ms = 0.f;
 	u32 rc_launches = 0;
 	hipEvent_t ev[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
+	hipEvent_t col_ev = nullptr;     // dsrcgpu_compress_columns_device: in front of its check pass, so that batch_ms spans the text front end too
 	// per-stage HIP-event timing of the last batch: pairs of events around every k_sort launch and every replay group
 	std::vector<hipEvent_t> stage_ev; std::vector<u32> stage_kind; u32 stage_used = 0;       // kind: 0 sort, 1 replay
 	float sort_ms = 0.f, replay_ms = 0.f, decode_stream_ms = 0.f;
@@ -1768,6 +1770,7 @@ void dsrcgpu_destroy(dsrcgpu_handle* h)
 	if (h->dec_tables) hipFree(h->dec_tables);
 	if (h->d_crc_tab) hipFree(h->d_crc_tab);
 	for (int i = 0; i < 5; ++i) if (h->ev[i]) hipEventDestroy(h->ev[i]);
+	if (h->col_ev) hipEventDestroy(h->col_ev);
 	for (hipEvent_t e : h->stage_ev) hipEventDestroy(e);
 	if (h->rc_stream) hipStreamDestroy(h->rc_stream);
 	if (h->stream) hipStreamDestroy(h->stream);
@@ -2042,6 +2045,158 @@ int dsrcgpu_decompress_batch_columns_device(dsrcgpu_handle* h, uint32_t n, const
 		io.cols = out; io.col_block_records = block_records; io.col_totals = totals;
 		return run_decode(h, io);
 	});
+}
+
+} // extern "C"
+
+namespace
+{
+// ---- columnar encode (k_columns_enc.h) -------------------------------------------------------------------------------------------
+const char* const cole_reason[] = {"d_seq_offs is not non-decreasing", "d_seq_offs runs above bases_len", "d_title_offs is not non-decreasing",
+	"d_title_offs runs above titles_len", "empty title", "title does not start with '@'", "title contains a newline",
+	"base code above 18", "quality + quality_offset above 126"};
+
+int col_input_error(dsrcgpu_handle* h, u64 word)
+{
+	const u32 why = (u32)(word & 15u);
+	return fail(h, DSRCGPU_E_INPUT, "columns: record %llu: %s", (unsigned long long)(word >> 4), why < 9 ? cole_reason[why] : "?");
+}
+
+int col_in_args(dsrcgpu_handle* h, const dsrcgpu_columns_in* in, ColIn& c)
+{
+	if (!in) return fail(h, DSRCGPU_E_ARG, "null argument");
+	if (h->ds.color_space) return fail(h, DSRCGPU_E_ARG, "columns are defined for base space: a colour-space line is a primer plus colours");
+	if ((in->n_records | in->bases_len | in->titles_len) >> 56) return fail(h, DSRCGPU_E_ARG, "columns: array lengths of 2^56 and more");
+	if (in->n_records && (!in->d_seq_offs || !in->d_title_offs)) return fail(h, DSRCGPU_E_ARG, "columns: null offset array");
+	if ((in->bases_len && (!in->d_bases || !in->d_quals)) || (in->titles_len && !in->d_titles)) return fail(h, DSRCGPU_E_ARG, "columns: null array with a length");
+	c = ColIn{in->d_bases, in->d_quals, in->d_titles, in->d_seq_offs, in->d_title_offs, in->n_records, in->bases_len, in->titles_len,
+	          h->ds.plus_repetition ? 1u : 0u, h->ds.quality_offset};
+	return DSRCGPU_OK;
+}
+} // namespace
+
+extern "C" {
+
+// The check pass and the cut points' text positions first (one synchronisation brings both home), then the text is laid out like the
+// chunks of compress_batch_host, scattered into the arena and handed to run_batch as the library's own copy.
+int dsrcgpu_compress_columns_device(dsrcgpu_handle* h, uint32_t n, const dsrcgpu_columns_in* in, const uint64_t* block_records,
+									void* d_blocks, uint64_t blocks_cap, uint64_t* block_offs, uint64_t* block_sizes,
+									uint64_t* raw_sizes, uint64_t* comp_sizes)
+{
+	if (!h) return DSRCGPU_E_ARG;
+	if (h->ds.color_space) return fail(h, DSRCGPU_E_ARG, "columns are defined for base space: a colour-space line is a primer plus colours");
+	{
+		std::vector<u32> layout;
+		const int rc = user_batch_begin(h, layout);
+		if (rc) return rc;
+		if (!layout.empty()) return fail(h, DSRCGPU_E_ARG, "columns: a record layout is pending (dsrcgpu_set_record_layout belongs to the text calls of the archive API); dropped");
+	}
+	if (n == 0) return DSRCGPU_OK;
+	if (!block_records || !d_blocks || !block_offs || !block_sizes || !raw_sizes || !comp_sizes) return fail(h, DSRCGPU_E_ARG, "null argument");
+	ColIn c;
+	{ const int rc = col_in_args(h, in, c); if (rc) return rc; }
+	if (block_records[0] != 0 || block_records[n] != c.n_recs) return fail(h, DSRCGPU_E_ARG, "columns: block_records must run from 0 to n_records");
+	u64 max_recs = 1;
+	for (u32 i = 0; i < n; ++i)
+	{
+		if (block_records[i] >= block_records[i + 1]) return fail(h, DSRCGPU_E_ARG, "columns: block %u has no records (block_records must increase)", i);
+		max_recs = std::max<u64>(max_recs, block_records[i + 1] - block_records[i]);
+	}
+	HIPCHK(hipSetDevice(h->device));
+	hipStream_t s = h->stream;
+
+	// ---- check pass (the arena as it stands is large enough for it, except on a handle's first call) ----
+	std::vector<u64> res((size_t)n + 2);                 // error word, P at the n + 1 cut points
+	{
+		const int rc = ensure_arena(h, (size_t)(2 * (size_t)n + 3) * 8 + 1024);
+		if (rc) { chain_abort(h); return rc; }
+		if (!h->col_ev) HIPCHK(hipEventCreate(&h->col_ev));
+		HIPCHK(hipEventRecord(h->col_ev, s));
+		const size_t o_cut = h->arena.alloc(((size_t)n + 1) * 8), o_res = h->arena.alloc(((size_t)n + 2) * 8);
+		if (h->arena.failed) { chain_abort(h); return fail(h, DSRCGPU_E_NOMEM, "arena exhausted (columns check)"); }
+		u64* d_cut = AP<u64>(h, o_cut); u64* d_res = AP<u64>(h, o_res);
+		HIPCHK(hipMemcpyAsync(d_cut, block_records, ((size_t)n + 1) * 8, hipMemcpyHostToDevice, s));
+		HIPCHK(hipMemsetAsync(d_res, 0xFF, 8, s));
+		const u64 wpg = WG / 64;
+		const u32 gx = (u32)std::max<u64>(1, std::min<u64>(4096, (c.n_recs + wpg - 1) / wpg));
+		hipLaunchKernelGGL(k_col_check, dim3(gx), dim3(WG), 0, s, c, d_cut, n + 1, d_res + 1, d_res); KCHK();
+		HIPCHK(hipMemcpyAsync(res.data(), d_res, ((size_t)n + 2) * 8, hipMemcpyDeviceToHost, s));
+		HIPCHK(hipStreamSynchronize(s));
+	}
+	if (res[0] != COLE_NONE) { chain_abort(h); return col_input_error(h, res[0]); }
+
+	// ---- the chunks: sizes from P, laid out as compress_batch_host lays out the chunks it uploads ----
+	std::vector<u64> offs(n), sizes(n);
+	std::vector<ColEncBlk> blk(n);
+	size_t in_bytes = 0;
+	for (u32 i = 0; i < n; ++i)
+	{
+		sizes[i] = res[i + 2] - res[i + 1] - 1;
+		if (sizes[i] >= (1ull << 31)) { chain_abort(h); return fail(h, DSRCGPU_E_ARG, "columns: block %u: %llu bytes of text, the limit is 2^31 - 1; cut smaller blocks", i, (unsigned long long)sizes[i]); }
+		offs[i] = in_bytes; in_bytes += al((size_t)sizes[i] + 16, 256);
+		blk[i] = ColEncBlk{block_records[i], block_records[i + 1], res[i + 1], offs[i]};
+	}
+	const u32 gx = (u32)std::max<u64>(1, std::min<u64>(64, (max_recs + 4 * WAVES - 1) / (4 * WAVES)));
+	float front = 0.f;              // HIP-event time from in front of the check pass to the start of run_batch
+	const int rc_all = with_arena_retry(h, estimate_arena(h, n, sizes.data()) + in_bytes + (size_t)n * sizeof(ColEncBlk) + 1024, [&]() {
+		const size_t o_in = h->arena.alloc(in_bytes + 256), o_blk = h->arena.alloc(sizeof(ColEncBlk) * n);
+		if (h->arena.failed) return fail(h, DSRCGPU_E_NOMEM, "arena exhausted (text of the columns)");
+		u8* d_in = h->arena.base + o_in;
+		HIPCHK(hipMemcpyAsync(AP<ColEncBlk>(h, o_blk), blk.data(), sizeof(ColEncBlk) * n, hipMemcpyHostToDevice, s));
+		hipLaunchKernelGGL(k_col_scatter, dim3(gx, n), dim3(WG), 0, s, c, AP<ColEncBlk>(h, o_blk), d_in); KCHK();
+		BatchIO io{d_in, offs.data(), sizes.data(), n, (u8*)d_blocks, blocks_cap, nullptr, 0, block_offs, block_sizes, raw_sizes, comp_sizes, nullptr, false};
+		const int rc = run_batch(h, io);
+		if (rc == DSRCGPU_OK) hipEventElapsedTime(&front, h->col_ev, h->ev[0]);       // (before a verifying pass records ev[0] again)
+		if (rc != DSRCGPU_OK || !h->set.verify_after_compress || !h->set.calculate_crc32) return rc;
+		return verify_blocks(h, n, block_offs, block_sizes);
+	});
+	if (rc_all == DSRCGPU_OK)
+	{	// dsrcgpu_last_timing: from the check pass to k_assemble (the host's layout of the chunks between the two kernels included)
+		h->batch_ms += front;
+		if (getenv("DSRC_GPU_DEBUG")) fprintf(stderr, "[dsrc_gpu] columns: check pass, layout and scatter of %llu records took %.3f ms of the batch's %.3f\n", (unsigned long long)c.n_recs, front, h->batch_ms);
+	}
+	return rc_all;
+}
+
+int dsrcgpu_columns_cut(dsrcgpu_handle* h, const dsrcgpu_columns_in* in, uint64_t chunk_bytes, uint64_t* block_records, uint32_t cap, uint32_t* n)
+{
+	if (!h) return DSRCGPU_E_ARG;
+	if (!block_records || !n) return fail(h, DSRCGPU_E_ARG, "null argument");
+	*n = 0;
+	if (chunk_bytes == 0) return fail(h, DSRCGPU_E_ARG, "columns: chunk_bytes of 0");
+	ColIn c;
+	{ const int rc = col_in_args(h, in, c); if (rc) return rc; }
+	{
+		std::lock_guard<std::mutex> g(h->q_m);
+		if (h->q_started && h->q_pending) return fail(h, DSRCGPU_E_STATE, "batches of the queue form are still in flight on this handle");
+	}
+	if (c.n_recs == 0)
+	{
+		if (cap < 1) return fail(h, DSRCGPU_E_CAPACITY, "columns: block_records needs 1 entry, caller gave 0");
+		block_records[0] = 0;
+		return DSRCGPU_OK;
+	}
+	HIPCHK(hipSetDevice(h->device));
+	hipStream_t s = h->stream;
+	const u64 out_cap = std::min<u64>(cap, c.n_recs + 1);       // (no more blocks than records)
+	{ const int rc = ensure_arena(h, (size_t)(out_cap + 3) * 8 + 1024); if (rc) return rc; }
+	const size_t o_res = h->arena.alloc(16), o_out = h->arena.alloc((size_t)(out_cap + 1) * 8);
+	if (h->arena.failed) return fail(h, DSRCGPU_E_NOMEM, "arena exhausted (columns cut)");
+	u64* d_res = AP<u64>(h, o_res); u64* d_out = AP<u64>(h, o_out);       // d_res: error word, number of blocks
+	HIPCHK(hipMemsetAsync(d_res, 0xFF, 8, s));
+	HIPCHK(hipMemsetAsync(d_res + 1, 0, 8, s));
+	hipLaunchKernelGGL(k_col_mono, dim3((u32)std::max<u64>(1, std::min<u64>(1024, (c.n_recs + WG - 1) / WG))), dim3(WG), 0, s, c, d_res); KCHK();
+	hipLaunchKernelGGL(k_col_cut, dim3(1), dim3(64), 0, s, c, std::min<u64>(chunk_bytes, 1ull << 62), d_out, out_cap, d_res + 1, d_res); KCHK();
+	u64 res[2] = {0, 0};
+	HIPCHK(hipMemcpyAsync(res, d_res, 16, hipMemcpyDeviceToHost, s));
+	HIPCHK(hipStreamSynchronize(s));
+	if (res[0] != COLE_NONE) return col_input_error(h, res[0]);
+	if (res[1] >> 32) return fail(h, DSRCGPU_E_ARG, "columns: more than 2^32 - 1 blocks; raise chunk_bytes");
+	*n = (u32)res[1];
+	if (res[1] + 1 > cap) return fail(h, DSRCGPU_E_CAPACITY, "columns: block_records needs %llu entries, caller gave %u", (unsigned long long)(res[1] + 1), cap);
+	HIPCHK(hipMemcpyAsync(block_records, d_out, (size_t)(res[1] + 1) * 8, hipMemcpyDeviceToHost, s));
+	HIPCHK(hipStreamSynchronize(s));
+	return DSRCGPU_OK;
 }
 
 int dsrcgpu_decompress_batch(dsrcgpu_handle* h, uint32_t n, const uint8_t* const* blocks, const uint64_t* sizes, const uint64_t* text_caps,

@@ -159,6 +159,50 @@ int dsrcgpu_decompress_batch_columns_device(dsrcgpu_handle* h, uint32_t n, const
 		uint64_t* block_records /* n + 1: exclusive prefix of records per block */,
 		uint64_t totals[3]      /* records, bases, title bytes */, uint32_t* crc_ok);
 
+/* Columnar encode: the way back -- record arrays in HBM become DSRC blocks without the caller writing FASTQ text (no counterpart in
+ * the reference, whose writers take text or one record at a time: DsrcArchive::WriteNextRecord).  The arrays have the form
+ * dsrcgpu_decompress_batch_columns_device leaves behind; they are only read.  Block i holds records block_records[i] ..
+ * block_records[i + 1] - 1 and is bit-identical to the block dsrcgpu_compress_batch_device writes on the same handle for the chunk
+ * text of those records:  title \n letters \n plus \n qualities+quality_offset,  records joined by \n, no newline after the last;
+ * plus is "+", or "+" and the title without its '@' when the handle's dataset has plus_repetition.  That text is assembled in the
+ * handle's arena and goes through the same scheduler pass: raw_sizes / comp_sizes, the block-to-block state, tag_preserve_flags,
+ * calculate_crc32, verify_after_compress, chains and the codes for text the coder refuses are those of the text call (a read of
+ * length 0 gives empty lines, and whatever the text call answers to them).
+ * Offsets are relative to d_bases / d_titles as given and need not start at 0: d_seq_offs + k and d_title_offs + k of a decoded
+ * batch, with n_records reduced, compress a sub-range without a copy.
+ * A check pass on the device runs before any text is written and refuses, with DSRCGPU_E_INPUT, the lowest record index and the
+ * reason in dsrcgpu_last_error and d_blocks untouched: offsets out of order, a closing entry above bases_len / titles_len, a base code
+ * above 18, a quality q with q + quality_offset > 126, a title that is empty, does not start with '@' or contains '\n'.  No input
+ * makes a kernel read or write outside the caller's arrays.
+ * DSRCGPU_E_ARG: block_records not starting at 0, not strictly increasing (a block without records) or not ending at n_records; a
+ * block whose text reaches 2^31 bytes; a colour-space handle; a pending dsrcgpu_set_record_layout (the archive API's: it has no
+ * meaning here and is dropped by this call).  n == 0: DSRCGPU_OK.
+ * The call stays on the handle's own scheduler lane: it is never cut into sub-batches (dsrcgpu_set_lanes does not apply).  HBM: the
+ * arena of the text call for the same chunks plus the text itself. */
+typedef struct dsrcgpu_columns_in   /* device pointers owned by the caller, read only */
+{
+	const uint8_t*  d_bases;   uint64_t bases_len;    /* codes 0..18 = index in "ACGTNRWSKMDVHBYXU.-" (as dsrcgpu_columns) */
+	const uint8_t*  d_quals;                          /* quality character - quality_offset, same positions */
+	const uint8_t*  d_titles;  uint64_t titles_len;   /* title lines back to back, '@' included, no newline */
+	const uint64_t* d_seq_offs;                       /* n_records + 1 entries */
+	const uint64_t* d_title_offs;                     /* n_records + 1 entries */
+	uint64_t        n_records;
+} dsrcgpu_columns_in;
+
+int dsrcgpu_compress_columns_device(dsrcgpu_handle* h, uint32_t n, const dsrcgpu_columns_in* in,
+		const uint64_t* block_records /* n + 1, host: exclusive prefix, [n] == in->n_records */,
+		void* d_blocks, uint64_t blocks_cap, uint64_t* block_offs, uint64_t* block_sizes,
+		uint64_t* raw_sizes, uint64_t* comp_sizes);
+
+/* The cut a caller of the function above needs, because text sizes cannot be read off the arrays: greedily, each block takes as many
+ * consecutive records as keep its chunk text at or below chunk_bytes, and at least one.  The offset arrays stay on the device (a
+ * 64-way search per block).  block_records has room for `cap` entries; n blocks need n + 1 (the exclusive prefix, [n] ==
+ * n_records).  Too few: DSRCGPU_E_CAPACITY, *n = the number of blocks, nothing written.  Offsets out of order or a closing entry above
+ * bases_len / titles_len: DSRCGPU_E_INPUT.  chunk_bytes == 0 or a colour-space handle: DSRCGPU_E_ARG.  No records: *n = 0,
+ * block_records[0] = 0.  d_bases, d_quals and d_titles are not read. */
+int dsrcgpu_columns_cut(dsrcgpu_handle* h, const dsrcgpu_columns_in* in, uint64_t chunk_bytes,
+		uint64_t* block_records, uint32_t cap /* entries */, uint32_t* n /* blocks */);
+
 /* Queue form of DsrcCompressor::Process (src/DsrcWorker.cpp:39-70):
  *   fastqQueue.Pop(partId, chunk)            -> dsrcgpu_submit(partId, chunk)      (bytes are copied into page-locked staging)
  *   ... Store ... dsrcQueue.Push(partId, blk) -> dsrcgpu_collect(&partId, &blk, ...)
@@ -264,7 +308,8 @@ int dsrcgpu_host_free(void* p);
 int dsrcgpu_selftest(dsrcgpu_handle* h, uint32_t* mismatches);
 
 /* Timing of the last batch measured with HIP events on the scheduler's stream: total ms of the batch's
- * kernels, ms of the range-coder kernel (k_rc), number of k_rc launches. */
+ * kernels, ms of the range-coder kernel (k_rc), number of k_rc launches.  After dsrcgpu_compress_columns_device the batch figure starts
+ * in front of the check pass: it includes the check, the host's layout of the chunks and the scatter of the text. */
 int dsrcgpu_last_timing(const dsrcgpu_handle* h, float* batch_ms, float* rc_ms, uint32_t* rc_launches);
 
 /* ... and of the two data-parallel stages that bound the throughput of the order-context levels: summed HIP-event time
