@@ -26,6 +26,7 @@ EXPORTS = [
     "dsrcgpu_chain_seed", "dsrcgpu_last_stage_timing", "dsrcgpu_try_collect", "dsrcgpu_prepare", "dsrcgpu_set_table_budget", "dsrcgpu_device_memory", "dsrcgpu_release_memory",
     "dsrcgpu_synth_fastq", "dsrcgpu_reserve_memory", "dsrcgpu_set_lanes", "dsrcgpu_submit_pinned",
     "dsrcgpu_decompress_batch_columns_device", "dsrcgpu_compress_columns_device", "dsrcgpu_columns_cut",
+    "dsrcgpu_columns_trim_plan", "dsrcgpu_columns_select_device",
 ]
 
 # error codes of include/dsrc_gpu.h that callers tell apart (DsrcGpuError.code)
@@ -62,6 +63,16 @@ class ColumnsIn(C.Structure):
     """dsrcgpu_columns_in: the caller's device arrays of dsrcgpu_compress_columns_device / dsrcgpu_columns_cut (read only)."""
     _fields_ = [("d_bases", C.c_void_p), ("bases_len", C.c_uint64), ("d_quals", C.c_void_p), ("d_titles", C.c_void_p),
                 ("titles_len", C.c_uint64), ("d_seq_offs", C.c_void_p), ("d_title_offs", C.c_void_p), ("n_records", C.c_uint64)]
+
+
+class TrimRules(C.Structure):
+    """dsrcgpu_trim_rules: cutoffs of the running-sum trim (0 = that end is not trimmed) and the keep rules of
+    dsrcgpu_columns_trim_plan (max_n 0xFFFFFFFF = no limit, min_mean_quality 0 = off)."""
+    _fields_ = [("quality_5", C.c_uint32), ("quality_3", C.c_uint32), ("min_length", C.c_uint32), ("max_n", C.c_uint32),
+                ("min_mean_quality", C.c_uint32), ("reserved", C.c_uint32 * 3)]
+
+
+TRIM_STATS = ("records_kept", "bases_kept", "bases_cut", "dropped_length", "dropped_n", "dropped_mean_quality")
 
 
 class HostColumns(typing.NamedTuple):
@@ -376,6 +387,78 @@ class Handle:
             d_out = self.dev_alloc(cap); held.append(d_out)
             offs, sizes, _, _ = self.compress_columns_device(cin, block_records, d_out, cap)
             return [self.dev_download(d_out + o, s) for o, s in zip(offs, sizes)]
+        finally:
+            for p in held:
+                self.dev_free(p)
+
+    def columns_trim_plan(self, cols_in: ColumnsIn, rules: TrimRules, d_begin: int, d_end: int, d_keep: int):
+        """dsrcgpu_columns_trim_plan: the kept range of every record of `cols_in` into d_begin / d_end (uint64 each) and its keep
+        flag into d_keep (uint8), all device memory of n_records entries.  Returns the six statistics (TRIM_STATS names them)."""
+        stats = (C.c_uint64 * 6)()
+        self._chk(self.L.dsrcgpu_columns_trim_plan(self.h, C.byref(cols_in), C.byref(rules), C.c_void_p(d_begin), C.c_void_p(d_end),
+                                                   C.c_void_p(d_keep), stats))
+        return list(stats)
+
+    def columns_select_device(self, cols_in: ColumnsIn, d_begin, d_end, d_keep, out: Columns, d_source=None):
+        """dsrcgpu_columns_select_device: the kept records of `cols_in`, cut to [begin, end), compacted into the device arrays `out`
+        (d_begin / d_end / d_keep / d_source: device addresses or None).  Returns totals (records, bases, title bytes kept);
+        DsrcGpuError.code == E_CAPACITY when an array is too small -- `need` of the exception then holds the totals."""
+        totals = (C.c_uint64 * 3)()
+        rc = self.L.dsrcgpu_columns_select_device(self.h, C.byref(cols_in), C.c_void_p(d_begin), C.c_void_p(d_end), C.c_void_p(d_keep),
+                                                  C.byref(out), C.c_void_p(d_source), totals)
+        if rc < 0:
+            e = DsrcGpuError(rc, self.L.dsrcgpu_last_error(self.h).decode())
+            e.need = list(totals) if rc == E_CAPACITY else None
+            raise e
+        return list(totals)
+
+    def select_columns(self, cols, begin=None, end=None, keep=None, titles=True, return_source=False):
+        """Host convenience over columns_select_device: `cols` has numpy arrays bases, quals, titles, seq_offsets, title_offsets (a
+        HostColumns, or anything shaped like it), begin / end / keep are numpy arrays or None; everything is staged in HBM, sized
+        with a first call, selected, and the compacted arrays come back as a HostColumns (block_records = [0, kept], crc_ok None);
+        return_source=True: -> (HostColumns, source), source[j] = the index in `cols` of output record j."""
+        import numpy as np
+        held = []
+
+        def alloc(nbytes):
+            p = self.dev_alloc(max(nbytes, 8)); held.append(p)
+            return p
+
+        def stage(a, dtype):
+            if a is None:
+                return None
+            data = np.ascontiguousarray(a, dtype=dtype).tobytes()
+            p = alloc(len(data))
+            if data:
+                self.dev_upload(p, data)
+            return p
+
+        def fetch(ptr, count, dtype):
+            nbytes = count * np.dtype(dtype).itemsize
+            return np.frombuffer(self.dev_download(ptr, nbytes), dtype=dtype).copy() if nbytes else np.zeros(0, dtype)
+        try:
+            R = len(cols.seq_offsets) - 1
+            cin = ColumnsIn(stage(cols.bases, np.uint8), len(cols.bases), stage(cols.quals, np.uint8),
+                            stage(cols.titles, np.uint8) if titles else None, len(cols.titles) if titles else 0,
+                            stage(cols.seq_offsets, np.uint64), stage(cols.title_offsets, np.uint64) if titles else None, R)
+            d_begin, d_end, d_keep = stage(begin, np.uint64), stage(end, np.uint64), stage(keep, np.uint8)
+            spare = alloc(8)
+            need = [0, 0, 0]
+            try:
+                self.columns_select_device(cin, d_begin, d_end, d_keep, Columns(d_titles=spare if titles else None))
+            except DsrcGpuError as e:
+                if e.code != E_CAPACITY:
+                    raise
+                need = e.need
+            K, S, T = need
+            out = Columns(alloc(S), S, alloc(S), S, alloc(T) if titles else None, T if titles else 0,
+                          alloc(8 * (K + 1)), alloc(8 * (K + 1)) if titles else None, K)
+            d_source = alloc(8 * K)
+            totals = self.columns_select_device(cin, d_begin, d_end, d_keep, out, d_source)
+            got = HostColumns(fetch(out.d_bases, S, np.uint8), fetch(out.d_quals, S, np.uint8),
+                              fetch(out.d_titles, T, np.uint8) if titles else None, fetch(out.d_seq_offs, K + 1, np.uint64),
+                              fetch(out.d_title_offs, K + 1, np.uint64) if titles else None, [0, K], totals, None)
+            return (got, fetch(d_source, K, np.uint64)) if return_source else got
         finally:
             for p in held:
                 self.dev_free(p)

@@ -1,5 +1,6 @@
-"""Records as torch tensors: decode_columns (dsrcgpu_decompress_batch_columns_device) and the way back, encode_columns
-(dsrcgpu_compress_columns_device), include/dsrc_gpu.h.
+"""Records as torch tensors: decode_columns (dsrcgpu_decompress_batch_columns_device), the way back, encode_columns
+(dsrcgpu_compress_columns_device), and what runs between the two: trim_plan (dsrcgpu_columns_trim_plan), select_columns
+(dsrcgpu_columns_select_device) and filter_columns, include/dsrc_gpu.h.
 
 The blocks are already in device memory; the arrays are allocated by torch on the same device and filled by the library's
 kernels -- no text, no host round trip of the payload.  With the emulator build of the library (tests/emu) device pointers
@@ -101,3 +102,92 @@ def encode_columns(handle: _lib.Handle, cols: RecordColumns, block_records=None,
     quiesce()
     offs, sizes, _, _ = handle.compress_columns_device(cin, block_records, blocks.data_ptr(), cap)
     return blocks, offs, sizes, block_records
+
+
+def _columns_in(cols: RecordColumns, titles: bool):
+    """-> (_lib.ColumnsIn over the tensors of `cols`, the tensors to keep alive while it is in use)."""
+    device = cols.bases.device
+    spare = torch.empty(8, dtype=torch.uint8, device=device)
+    ptr = lambda t: t.data_ptr() if t.numel() else spare.data_ptr()
+    held = [t.contiguous() for t in (cols.bases, cols.quals, cols.titles, cols.seq_offsets, cols.title_offsets)] + [spare]
+    bases, quals, title_bytes, seq_offs, title_offs = held[:5]
+    R = cols.n_records
+    if titles and title_offs.numel() != R + 1:
+        raise ValueError("these columns have no titles (decode_columns(..., titles=False))")
+    cin = _lib.ColumnsIn(ptr(bases), bases.numel(), ptr(quals), ptr(title_bytes) if titles else None, title_bytes.numel() if titles else 0,
+                         seq_offs.data_ptr(), title_offs.data_ptr() if titles else None, R)
+    return cin, held
+
+
+def _quiesce(device):       # as in decode_columns: the library works on its own stream
+    if device.type == "cuda":
+        torch.cuda.current_stream(device).synchronize()
+
+
+def trim_plan(handle: _lib.Handle, cols: RecordColumns, quality_5: int = 0, quality_3: int = 0, min_length: int = 1, max_n=None,
+              min_mean_quality: int = 0):
+    """dsrcgpu_columns_trim_plan on the records of `cols`: -> (begin, end, keep, stats).  begin / end (int64) are the kept range of
+    every record as positions in cols.bases, keep (uint8) is 1 for the records that pass the rules, stats is a dict with the keys
+    of _lib.TRIM_STATS.  quality_5 / quality_3: Phred cutoffs of the running-sum trim, 0 = that end is left alone; max_n=None: no
+    limit on bases other than A C G T.  Nothing of the payload crosses to the host."""
+    device = cols.bases.device
+    R = cols.n_records
+    cin, held = _columns_in(cols, titles=False)
+    begin = torch.empty(R, dtype=torch.int64, device=device); end = torch.empty(R, dtype=torch.int64, device=device)
+    keep = torch.empty(R, dtype=torch.uint8, device=device)
+    rules = _lib.TrimRules(quality_5, quality_3, min_length, 0xFFFFFFFF if max_n is None else max_n, min_mean_quality)
+    _quiesce(device)
+    stats = handle.columns_trim_plan(cin, rules, begin.data_ptr(), end.data_ptr(), keep.data_ptr())
+    del held
+    return begin, end, keep, dict(zip(_lib.TRIM_STATS, stats))
+
+
+def select_columns(handle: _lib.Handle, cols: RecordColumns, begin=None, end=None, keep=None, titles: bool = True, return_source: bool = False):
+    """dsrcgpu_columns_select_device: the records of `cols` with a non-zero `keep` entry (None: all), bases and qualities cut to
+    [begin[r], end[r]) (None: whole reads), titles whole, compacted into new tensors on the same device -> RecordColumns with
+    block_records = [0, kept]; return_source=True: -> (RecordColumns, source), source[j] = the index in `cols` of output record j.
+    begin / end are int64 (or uint64-valued) tensors, keep a uint8 or bool tensor, as trim_plan returns them.  The first library call
+    sizes the arrays, the second one fills them."""
+    device = cols.bases.device
+    if (begin is None) != (end is None):
+        raise ValueError("begin and end go together")
+    cin, held = _columns_in(cols, titles)
+    if begin is not None:
+        begin = begin.to(torch.int64).contiguous(); end = end.to(torch.int64).contiguous()
+    if keep is not None:
+        keep = keep.to(torch.uint8).contiguous()
+    for t in (begin, end, keep):
+        if t is not None and (t.numel() != cols.n_records or t.device != device):
+            raise ValueError("begin, end and keep have one entry per record, on the device of the columns")
+    adr = lambda t: None if t is None or not t.numel() else t.data_ptr()
+    spare = held[-1]
+    _quiesce(device)
+    need = [0, 0, 0]
+    try:
+        handle.columns_select_device(cin, adr(begin), adr(end), adr(keep), _lib.Columns(d_titles=spare.data_ptr() if titles else None))
+    except _lib.DsrcGpuError as e:
+        if e.code != _lib.E_CAPACITY:
+            raise
+        need = e.need
+    K, S, T = need
+    u8 = dict(dtype=torch.uint8, device=device); i64 = dict(dtype=torch.int64, device=device)
+    bases = torch.empty(S, **u8); quals = torch.empty(S, **u8)
+    seq_offsets = torch.empty(K + 1, **i64)
+    title_bytes = torch.empty(T if titles else 0, **u8)
+    title_offsets = torch.empty(K + 1 if titles else 0, **i64)
+    source = torch.empty(K, **i64)
+    ptr = lambda t: t.data_ptr() if t.numel() else spare.data_ptr()
+    out = _lib.Columns(ptr(bases), S, ptr(quals), S, ptr(title_bytes) if titles else None, T if titles else 0,
+                       seq_offsets.data_ptr(), title_offsets.data_ptr() if titles else None, K)
+    _quiesce(device)
+    totals = handle.columns_select_device(cin, adr(begin), adr(end), adr(keep), out, adr(source) if return_source else None)
+    assert totals == need
+    del held
+    got = RecordColumns(bases, quals, title_bytes, seq_offsets, title_offsets, torch.tensor([0, K], **i64))
+    return (got, source) if return_source else got
+
+
+def filter_columns(handle: _lib.Handle, cols: RecordColumns, titles: bool = True, **rules):
+    """trim_plan(**rules) and select_columns with its plan in sequence: -> (RecordColumns of the trimmed, kept records, stats)."""
+    begin, end, keep, stats = trim_plan(handle, cols, **rules)
+    return select_columns(handle, cols, begin, end, keep, titles=titles), stats

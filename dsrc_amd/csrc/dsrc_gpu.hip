@@ -46,6 +46,7 @@
 #include "k_dec_q0.h"
 #include "k_columns.h"
 #include "k_columns_enc.h"
+#include "k_columns_sel.h"
 
 namespace
 {
@@ -2195,6 +2196,124 @@ int dsrcgpu_columns_cut(dsrcgpu_handle* h, const dsrcgpu_columns_in* in, uint64_
 	*n = (u32)res[1];
 	if (res[1] + 1 > cap) return fail(h, DSRCGPU_E_CAPACITY, "columns: block_records needs %llu entries, caller gave %u", (unsigned long long)(res[1] + 1), cap);
 	HIPCHK(hipMemcpyAsync(block_records, d_out, (size_t)(res[1] + 1) * 8, hipMemcpyDeviceToHost, s));
+	HIPCHK(hipStreamSynchronize(s));
+	return DSRCGPU_OK;
+}
+
+} // extern "C"
+
+namespace
+{
+// ---- columnar select (k_columns_sel.h) ---------------------------------------------------------------------------------------------
+// Both calls are scratch-only users of the handle's own lane: they take a few words per record from the arena, run on h->stream and
+// synchronise before they return; h->fields_cap, h->rec_pending and the chain are neither read nor written.
+int sel_input_error(dsrcgpu_handle* h, u64 word)
+{
+	static const char* const why_sel[] = {"d_begin lies below the record's first base", "d_end lies above the record's last base", "d_begin lies above d_end"};
+	const u32 why = (u32)(word & 15u);
+	if (why < COLS_BEGIN_LOW || why > COLS_RANGE_ORDER) return col_input_error(h, word);
+	return fail(h, DSRCGPU_E_INPUT, "columns: record %llu: %s", (unsigned long long)(word >> 4), why_sel[why - COLS_BEGIN_LOW]);
+}
+
+// col_in_args for the calls that may do without the titles
+int sel_in_args(dsrcgpu_handle* h, const dsrcgpu_columns_in* in, bool titles, ColIn& c)
+{
+	if (!in) return fail(h, DSRCGPU_E_ARG, "null argument");
+	if (h->ds.color_space) return fail(h, DSRCGPU_E_ARG, "columns are defined for base space: a colour-space line is a primer plus colours");
+	if ((in->n_records | in->bases_len | (titles ? in->titles_len : 0)) >> 56) return fail(h, DSRCGPU_E_ARG, "columns: array lengths of 2^56 and more");
+	if (in->n_records && (!in->d_seq_offs || (titles && !in->d_title_offs))) return fail(h, DSRCGPU_E_ARG, "columns: null offset array");
+	if ((in->bases_len && (!in->d_bases || !in->d_quals)) || (titles && in->titles_len && !in->d_titles)) return fail(h, DSRCGPU_E_ARG, "columns: null array with a length");
+	c = ColIn{in->d_bases, in->d_quals, titles ? in->d_titles : nullptr, in->d_seq_offs, titles ? in->d_title_offs : nullptr, in->n_records, in->bases_len,
+	          titles ? in->titles_len : 0, h->ds.plus_repetition ? 1u : 0u, h->ds.quality_offset};
+	{
+		std::lock_guard<std::mutex> g(h->q_m);
+		if (h->q_started && h->q_pending) return fail(h, DSRCGPU_E_STATE, "batches of the queue form are still in flight on this handle");
+	}
+	return DSRCGPU_OK;
+}
+} // namespace
+
+extern "C" {
+
+int dsrcgpu_columns_trim_plan(dsrcgpu_handle* h, const dsrcgpu_columns_in* in, const dsrcgpu_trim_rules* rules,
+							  uint64_t* d_begin, uint64_t* d_end, uint8_t* d_keep, uint64_t stats[6])
+{
+	if (!h) return DSRCGPU_E_ARG;
+	if (!rules || !stats) return fail(h, DSRCGPU_E_ARG, "null argument");
+	for (u32 k = 0; k < 6; ++k) stats[k] = 0;
+	ColIn c;
+	{ const int rc = sel_in_args(h, in, false, c); if (rc) return rc; }
+	if (rules->quality_5 > 255 || rules->quality_3 > 255) return fail(h, DSRCGPU_E_ARG, "trim rules: a quality cutoff above 255");
+	if (rules->reserved[0] | rules->reserved[1] | rules->reserved[2]) return fail(h, DSRCGPU_E_ARG, "trim rules: reserved fields must be 0");
+	if (c.n_recs == 0) return DSRCGPU_OK;
+	if (!d_begin || !d_end || !d_keep) return fail(h, DSRCGPU_E_ARG, "null argument");
+	HIPCHK(hipSetDevice(h->device));
+	hipStream_t s = h->stream;
+	{ const int rc = ensure_arena(h, 7 * 8 + 1024); if (rc) return rc; }
+	const size_t o_res = h->arena.alloc(7 * 8);
+	if (h->arena.failed) return fail(h, DSRCGPU_E_NOMEM, "arena exhausted (trim plan)");
+	u64* d_res = AP<u64>(h, o_res);                      // error word, the six statistics
+	HIPCHK(hipMemsetAsync(d_res, 0xFF, 8, s));
+	HIPCHK(hipMemsetAsync(d_res + 1, 0, 6 * 8, s));
+	const TrimRules R{rules->quality_5, rules->quality_3, rules->min_length, rules->max_n, rules->min_mean_quality};
+	const u64 wpg = WG / 64;
+	hipLaunchKernelGGL(k_sel_seq_check, dim3((u32)std::max<u64>(1, std::min<u64>(1024, (c.n_recs + WG - 1) / WG))), dim3(WG), 0, s, c, d_res); KCHK();
+	hipLaunchKernelGGL(k_sel_plan, dim3((u32)std::max<u64>(1, std::min<u64>(4096, (c.n_recs + wpg - 1) / wpg))), dim3(WG), 0, s, c, R, d_begin, d_end, d_keep, d_res + 1, d_res); KCHK();
+	u64 res[7];
+	HIPCHK(hipMemcpyAsync(res, d_res, sizeof(res), hipMemcpyDeviceToHost, s));
+	HIPCHK(hipStreamSynchronize(s));
+	if (res[0] != COLE_NONE) return sel_input_error(h, res[0]);
+	for (u32 k = 0; k < 6; ++k) stats[k] = res[k + 1];
+	return DSRCGPU_OK;
+}
+
+// tile sums and their scan first: error word and totals come home in one synchronisation, in front of the first kernel that writes the
+// caller's arrays
+int dsrcgpu_columns_select_device(dsrcgpu_handle* h, const dsrcgpu_columns_in* in, const uint64_t* d_begin, const uint64_t* d_end,
+								  const uint8_t* d_keep, const dsrcgpu_columns* out, uint64_t* d_source, uint64_t totals[3])
+{
+	if (!h) return DSRCGPU_E_ARG;
+	if (!out || !totals) return fail(h, DSRCGPU_E_ARG, "null argument");
+	totals[0] = totals[1] = totals[2] = 0;
+	if (!d_begin != !d_end) return fail(h, DSRCGPU_E_ARG, "columns: d_begin and d_end go together");
+	if (!out->d_titles && out->titles_cap) return fail(h, DSRCGPU_E_ARG, "columns: titles_cap without d_titles");
+	const bool titles = out->d_titles != nullptr;
+	ColIn c;
+	{ const int rc = sel_in_args(h, in, titles, c); if (rc) return rc; }
+	HIPCHK(hipSetDevice(h->device));
+	hipStream_t s = h->stream;
+	const auto nothing_kept = [&]() -> int {
+		if (out->d_seq_offs) HIPCHK(hipMemsetAsync(out->d_seq_offs, 0, sizeof(u64), s));
+		if (titles && out->d_title_offs) HIPCHK(hipMemsetAsync(out->d_title_offs, 0, sizeof(u64), s));
+		HIPCHK(hipStreamSynchronize(s));
+		return DSRCGPU_OK;
+	};
+	if (c.n_recs == 0) return nothing_kept();
+	const u64 n_tiles = (c.n_recs + WG - 1) / WG;
+	{ const int rc = ensure_arena(h, (size_t)(3 * n_tiles + c.n_recs + 4) * 8 + 4096); if (rc) return rc; }
+	const size_t o_res = h->arena.alloc(4 * 8), o_tiles = h->arena.alloc((size_t)n_tiles * 24), o_pos = h->arena.alloc((size_t)c.n_recs * 8);
+	if (h->arena.failed) return fail(h, DSRCGPU_E_NOMEM, "arena exhausted (columns select)");
+	u64* d_res = AP<u64>(h, o_res); u64* d_tiles = AP<u64>(h, o_tiles); u64* d_pos = AP<u64>(h, o_pos);      // d_res: error word, the three totals
+	const SelWhat w{d_begin, d_end, d_keep, titles ? 1u : 0u};
+	const u32 g_tiles = (u32)std::min<u64>(4096, n_tiles);
+	HIPCHK(hipMemsetAsync(d_res, 0xFF, 8, s));
+	hipLaunchKernelGGL(k_sel_tiles, dim3(g_tiles), dim3(WG), 0, s, c, w, n_tiles, d_tiles, d_res); KCHK();
+	hipLaunchKernelGGL(k_sel_scan_tiles, dim3(1), dim3(WG), 0, s, n_tiles, d_tiles, d_res + 1); KCHK();
+	u64 res[4];
+	HIPCHK(hipMemcpyAsync(res, d_res, sizeof(res), hipMemcpyDeviceToHost, s));
+	HIPCHK(hipStreamSynchronize(s));
+	if (res[0] != COLE_NONE) return sel_input_error(h, res[0]);
+	totals[0] = res[1]; totals[1] = res[2]; totals[2] = res[3];
+	if (out->records_cap < res[1] || out->bases_cap < res[2] || out->quals_cap < res[2] || (titles && out->titles_cap < res[3]))
+		return fail(h, DSRCGPU_E_CAPACITY, "columns: %llu records, %llu bases, %llu title bytes are kept; the caller's arrays hold %llu, %llu / %llu, %llu",
+		            (unsigned long long)res[1], (unsigned long long)res[2], (unsigned long long)res[3], (unsigned long long)out->records_cap,
+		            (unsigned long long)out->bases_cap, (unsigned long long)out->quals_cap, (unsigned long long)out->titles_cap);
+	if (res[1] == 0) return nothing_kept();
+	if (!out->d_seq_offs || (titles && !out->d_title_offs) || (res[2] && (!out->d_bases || !out->d_quals))) return fail(h, DSRCGPU_E_ARG, "columns: null output array");
+	const SelOut o{out->d_bases, out->d_quals, out->d_titles, out->d_seq_offs, out->d_title_offs, d_source, res[1], res[2], res[3]};
+	const u64 wpg = WG / 64;
+	hipLaunchKernelGGL(k_sel_apply, dim3(g_tiles), dim3(WG), 0, s, c, w, n_tiles, d_tiles, o, d_pos); KCHK();
+	hipLaunchKernelGGL(k_sel_gather, dim3((u32)std::max<u64>(1, std::min<u64>(4096, (c.n_recs + wpg - 1) / wpg))), dim3(WG), 0, s, c, w, o, d_pos); KCHK();
 	HIPCHK(hipStreamSynchronize(s));
 	return DSRCGPU_OK;
 }

@@ -203,6 +203,57 @@ int dsrcgpu_compress_columns_device(dsrcgpu_handle* h, uint32_t n, const dsrcgpu
 int dsrcgpu_columns_cut(dsrcgpu_handle* h, const dsrcgpu_columns_in* in, uint64_t chunk_bytes,
 		uint64_t* block_records, uint32_t cap /* entries */, uint32_t* n /* blocks */);
 
+/* Columnar select: what runs between the two calls above -- a quality trim / read filter that plans, and a ragged compaction that
+ * carries the plan (or any plan of the caller's) out, both in HBM (no counterpart in the reference, whose readers hand out text one
+ * record at a time).  Both calls only read `in`; offsets are relative to the arrays as given and need not start at 0 (d_seq_offs + k
+ * works as above).  Both run on the handle's own scheduler lane and stream, take their scratch (a few words per record) from the
+ * handle's arena and synchronise before they return.  Neither reads, changes or consumes codec state: the fields capacity and a
+ * pending dsrcgpu_set_record_layout are after the call what they were before it.  A colour-space handle: DSRCGPU_E_ARG.
+ *
+ * dsrcgpu_columns_trim_plan: per record the range [begin, end) of positions in d_bases / d_quals that survives trimming,
+ * S[r] <= begin <= end <= S[r + 1] with S = d_seq_offs, and whether the record is kept.  d_titles and d_title_offs are not read and
+ * may be NULL.  Trimming is the running-sum ("BWA") rule on d_quals (Phred values: the quality offset is already gone), each end
+ * computed by itself on the whole read.  5' end with cutoff c: s = 0; for i = 0, 1, ...: s += c - q[i]; stop at the first s < 0; start
+ * = i + 1 for the first i at which s reached its maximum above 0 (else 0).  3' end: the same from the last base backwards, stop = that
+ * i (else the length).  start >= stop: the range is empty, begin = end = S[r].  A record is kept iff, in this order, it has at least
+ * min_length bases in the range, at most max_n of them with a code >= 4, and a quality sum of at least min_mean_quality * length; the
+ * first rule that fails is the one counted in stats.
+ * stats (host): records kept, bases kept, bases cut off kept records, records dropped for length, for N, for mean quality.
+ * n_records == 0: DSRCGPU_OK, stats 0.  d_seq_offs out of order or a closing entry above bases_len: DSRCGPU_E_INPUT, the lowest record
+ * and the reason in dsrcgpu_last_error, nothing written.  A cutoff above 255 or a non-zero reserved field: DSRCGPU_E_ARG.  No input
+ * makes a kernel read outside the caller's arrays. */
+typedef struct dsrcgpu_trim_rules
+{
+	uint32_t quality_5, quality_3;   /* Phred cutoffs for the 5' / 3' end, 0 = that end is not trimmed; > 255: DSRCGPU_E_ARG */
+	uint32_t min_length;             /* keep a record iff it has at least this many bases after trimming */
+	uint32_t max_n;                  /* ... and at most this many bases with code >= 4 (anything but A C G T, 255 included) in the kept
+	                                    range; 0xFFFFFFFF = no limit */
+	uint32_t min_mean_quality;       /* ... and sum(q over the kept range) >= min_mean_quality * kept length; 0 = off */
+	uint32_t reserved[3];            /* must be 0, else DSRCGPU_E_ARG */
+} dsrcgpu_trim_rules;
+
+int dsrcgpu_columns_trim_plan(dsrcgpu_handle* h, const dsrcgpu_columns_in* in, const dsrcgpu_trim_rules* rules,
+		uint64_t* d_begin, uint64_t* d_end   /* device, n_records each */,
+		uint8_t* d_keep                      /* device, n_records: 1 / 0 */,
+		uint64_t stats[6]);
+
+/* dsrcgpu_columns_select_device: the records with a non-zero d_keep byte (NULL = all), in input order, bases and qualities cut to
+ * [d_begin[r], d_end[r]) (both NULL = whole reads), titles whole, compacted into `out` with offsets from 0: out->d_seq_offs and
+ * out->d_title_offs get kept + 1 entries.  d_source (device, may be NULL) gets the index in `in` of each kept record.  totals (host):
+ * records kept, bases kept, title bytes kept.
+ * Capacities as in dsrcgpu_decompress_batch_columns_device: any too small: DSRCGPU_E_CAPACITY, totals = what is needed, none of the
+ * caller's arrays written (the totals come home before the first writing kernel is launched); a call with capacities of 0 sizes the
+ * arrays.  out->d_titles == NULL with titles_cap 0: titles are not wanted, totals[2] is 0, in->d_titles and in->d_title_offs may be NULL
+ * (so a sizing call that wants the title total passes a non-null d_titles with titles_cap 0).
+ * DSRCGPU_E_INPUT (lowest record and reason in dsrcgpu_last_error, outputs untouched), for kept and dropped records alike: offsets out of
+ * order, a closing entry above bases_len / titles_len, d_begin[r] < S[r], d_end[r] > S[r + 1], d_begin[r] > d_end[r].
+ * Nothing kept, or n_records == 0: DSRCGPU_OK, totals 0, offs[0] = 0.
+ * The arrays of `in`, d_begin, d_end, d_keep on one side and the arrays of `out`, d_source on the other must not overlap; this is not
+ * checked. */
+int dsrcgpu_columns_select_device(dsrcgpu_handle* h, const dsrcgpu_columns_in* in,
+		const uint64_t* d_begin, const uint64_t* d_end, const uint8_t* d_keep,
+		const dsrcgpu_columns* out, uint64_t* d_source, uint64_t totals[3]);
+
 /* Queue form of DsrcCompressor::Process (src/DsrcWorker.cpp:39-70):
  *   fastqQueue.Pop(partId, chunk)            -> dsrcgpu_submit(partId, chunk)      (bytes are copied into page-locked staging)
  *   ... Store ... dsrcQueue.Push(partId, blk) -> dsrcgpu_collect(&partId, &blk, ...)
