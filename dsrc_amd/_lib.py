@@ -26,7 +26,7 @@ EXPORTS = [
     "dsrcgpu_chain_seed", "dsrcgpu_last_stage_timing", "dsrcgpu_try_collect", "dsrcgpu_prepare", "dsrcgpu_set_table_budget", "dsrcgpu_device_memory", "dsrcgpu_release_memory",
     "dsrcgpu_synth_fastq", "dsrcgpu_reserve_memory", "dsrcgpu_set_lanes", "dsrcgpu_submit_pinned",
     "dsrcgpu_decompress_batch_columns_device", "dsrcgpu_compress_columns_device", "dsrcgpu_columns_cut",
-    "dsrcgpu_columns_trim_plan", "dsrcgpu_columns_select_device",
+    "dsrcgpu_columns_trim_plan", "dsrcgpu_columns_select_device", "dsrcgpu_columns_adapter_plan",
 ]
 
 # error codes of include/dsrc_gpu.h that callers tell apart (DsrcGpuError.code)
@@ -73,6 +73,29 @@ class TrimRules(C.Structure):
 
 
 TRIM_STATS = ("records_kept", "bases_kept", "bases_cut", "dropped_length", "dropped_n", "dropped_mean_quality")
+
+
+class AdapterRules(C.Structure):
+    """dsrcgpu_adapter_rules: up to 8 adapters of 1 .. 64 base codes 0 .. 3 and the figures of dsrcgpu_columns_adapter_plan.
+    AdapterRules(adapters, min_overlap, max_error_permille, min_length): `adapters` is a list of bytes / sequences of codes.  Lists
+    too long to fit are cut to what fits with their count and lengths kept, so that the library is the one that refuses them."""
+    _fields_ = [("n_adapters", C.c_uint32), ("adapter_len", C.c_uint32 * 8), ("adapters", (C.c_uint8 * 64) * 8), ("min_overlap", C.c_uint32),
+                ("max_error_permille", C.c_uint32), ("min_length", C.c_uint32), ("reserved", C.c_uint32 * 3)]
+
+    def __init__(self, adapters=(), min_overlap=3, max_error_permille=100, min_length=1, reserved=(0, 0, 0)):
+        super().__init__()
+        adapters = [bytes(bytearray(a)) for a in adapters]
+        self.n_adapters = len(adapters)
+        for i, a in enumerate(adapters[:8]):
+            self.adapter_len[i] = len(a)
+            for j, code in enumerate(a[:64]):
+                self.adapters[i][j] = code
+        self.min_overlap, self.max_error_permille, self.min_length = min_overlap, max_error_permille, min_length
+        self.reserved = (C.c_uint32 * 3)(*reserved)
+
+
+ADAPTER_STATS = ("records_kept", "bases_kept", "bases_cut", "records_trimmed", "dropped_length") + tuple("found_%d" % a for a in range(8))
+NO_ADAPTER = 0xFFFFFFFF          # d_which of a record in which none was found
 
 
 class HostColumns(typing.NamedTuple):
@@ -397,6 +420,18 @@ class Handle:
         stats = (C.c_uint64 * 6)()
         self._chk(self.L.dsrcgpu_columns_trim_plan(self.h, C.byref(cols_in), C.byref(rules), C.c_void_p(d_begin), C.c_void_p(d_end),
                                                    C.c_void_p(d_keep), stats))
+        return list(stats)
+
+    def columns_adapter_plan(self, cols_in: ColumnsIn, rules: AdapterRules, d_begin_in, d_end_in, d_keep_in, d_begin: int, d_end: int,
+                             d_keep: int, d_which=None):
+        """dsrcgpu_columns_adapter_plan: the 3' adapter search on the plan d_begin_in / d_end_in / d_keep_in (device addresses or None:
+        whole reads, every record) into d_begin / d_end (uint64 each), d_keep (uint8) and, if wanted, d_which (uint32: the adapter
+        found, NO_ADAPTER for none), all device memory of n_records entries; an output may be the very array of its input.  Returns
+        the thirteen statistics (ADAPTER_STATS names them)."""
+        stats = (C.c_uint64 * 13)()
+        self._chk(self.L.dsrcgpu_columns_adapter_plan(self.h, C.byref(cols_in), C.byref(rules), C.c_void_p(d_begin_in), C.c_void_p(d_end_in),
+                                                      C.c_void_p(d_keep_in), C.c_void_p(d_begin), C.c_void_p(d_end), C.c_void_p(d_keep),
+                                                      C.c_void_p(d_which), stats))
         return list(stats)
 
     def columns_select_device(self, cols_in: ColumnsIn, d_begin, d_end, d_keep, out: Columns, d_source=None):

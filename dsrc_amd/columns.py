@@ -1,6 +1,6 @@
 """Records as torch tensors: decode_columns (dsrcgpu_decompress_batch_columns_device), the way back, encode_columns
-(dsrcgpu_compress_columns_device), and what runs between the two: trim_plan (dsrcgpu_columns_trim_plan), select_columns
-(dsrcgpu_columns_select_device) and filter_columns, include/dsrc_gpu.h.
+(dsrcgpu_compress_columns_device), and what runs between the two: trim_plan (dsrcgpu_columns_trim_plan), adapter_plan
+(dsrcgpu_columns_adapter_plan), select_columns (dsrcgpu_columns_select_device) and filter_columns, include/dsrc_gpu.h.
 
 The blocks are already in device memory; the arrays are allocated by torch on the same device and filled by the library's
 kernels -- no text, no host round trip of the payload.  With the emulator build of the library (tests/emu) device pointers
@@ -187,7 +187,85 @@ def select_columns(handle: _lib.Handle, cols: RecordColumns, begin=None, end=Non
     return (got, source) if return_source else got
 
 
-def filter_columns(handle: _lib.Handle, cols: RecordColumns, titles: bool = True, **rules):
-    """trim_plan(**rules) and select_columns with its plan in sequence: -> (RecordColumns of the trimmed, kept records, stats)."""
+_BASE_CODES = {"A": 0, "C": 1, "G": 2, "T": 3}
+
+
+def _adapter_codes(adapters):
+    """`adapters` (strs over ACGT in either case, or sequences of codes 0 .. 3) as a list of bytes; ValueError for anything else."""
+    if isinstance(adapters, (str, bytes, bytearray)) or not hasattr(adapters, "__len__"):
+        raise ValueError("adapters is a list of strings over ACGT or of sequences of base codes 0..3")
+    if not 1 <= len(adapters) <= 8:
+        raise ValueError("between 1 and 8 adapters are needed, %d given" % len(adapters))
+    out = []
+    for a in adapters:
+        if isinstance(a, str):
+            if any(ch not in _BASE_CODES for ch in a.upper()):
+                raise ValueError("adapter %r: only A, C, G and T are allowed" % a)
+            codes = [_BASE_CODES[ch] for ch in a.upper()]
+        else:
+            try:
+                codes = [int(v) for v in a]
+            except (TypeError, ValueError):
+                raise ValueError("adapter %r is neither a string nor a sequence of base codes" % (a,)) from None
+            if any(v < 0 or v > 3 for v in codes):
+                raise ValueError("adapter %r: base codes are 0..3" % (a,))
+        if not 1 <= len(codes) <= 64:
+            raise ValueError("an adapter has 1 to 64 bases, %d given" % len(codes))
+        out.append(bytes(codes))
+    return out
+
+
+def adapter_plan(handle: _lib.Handle, cols: RecordColumns, adapters, begin=None, end=None, keep=None, min_overlap: int = 3,
+                 max_error_permille: int = 100, min_length: int = 1, return_which: bool = False):
+    """dsrcgpu_columns_adapter_plan on the records of `cols`: the 3' adapter search on the plan begin / end / keep (None: whole
+    reads, every record; as trim_plan returns them) -> (begin, end, keep, stats[, which]) in fresh tensors.  `adapters`: up to 8 strs
+    over ACGT (either case) or sequences of codes 0 .. 3, 1 .. 64 bases each; anything else raises ValueError before the library is
+    called.  The leftmost start position at which an adapter -- or its first min_overlap and more bases, at the end of the range
+    -- matches with at most max_error_permille mismatches per 1000 compared bases becomes the new end; a record is kept iff it came
+    in kept and at least min_length bases are left.  stats is a dict with the keys of _lib.ADAPTER_STATS; which (int64) is the index
+    of the adapter found, -1 for none.  Nothing of the payload crosses to the host."""
+    codes = _adapter_codes(adapters)
+    for name, v, lo, hi in (("min_overlap", min_overlap, 1, min(len(c) for c in codes)), ("max_error_permille", max_error_permille, 0, 1000),
+                            ("min_length", min_length, 0, 0xFFFFFFFF)):
+        if not isinstance(v, int) or not lo <= v <= hi:
+            raise ValueError("%s must be an integer in %d..%d" % (name, lo, hi))
+    if (begin is None) != (end is None):
+        raise ValueError("begin and end go together")
+    device = cols.bases.device
+    R = cols.n_records
+    cin, held = _columns_in(cols, titles=False)
+    if begin is not None:
+        begin = begin.to(torch.int64).contiguous(); end = end.to(torch.int64).contiguous()
+    if keep is not None:
+        keep = keep.to(torch.uint8).contiguous()
+    for t in (begin, end, keep):
+        if t is not None and (t.numel() != R or t.device != device):
+            raise ValueError("begin, end and keep have one entry per record, on the device of the columns")
+    adr = lambda t: None if t is None or not t.numel() else t.data_ptr()
+    out_begin = torch.empty(R, dtype=torch.int64, device=device); out_end = torch.empty(R, dtype=torch.int64, device=device)
+    out_keep = torch.empty(R, dtype=torch.uint8, device=device)
+    which = torch.empty(R, dtype=torch.int32, device=device) if return_which else None
+    rules = _lib.AdapterRules(codes, min_overlap, max_error_permille, min_length)
+    _quiesce(device)
+    stats = handle.columns_adapter_plan(cin, rules, adr(begin), adr(end), adr(keep), out_begin.data_ptr(), out_end.data_ptr(), out_keep.data_ptr(),
+                                        adr(which))
+    del held
+    got = (out_begin, out_end, out_keep, dict(zip(_lib.ADAPTER_STATS, stats)))
+    return got + (which.to(torch.int64),) if return_which else got
+
+
+def filter_columns(handle: _lib.Handle, cols: RecordColumns, titles: bool = True, adapters=None, adapter_min_overlap: int = 3,
+                   adapter_max_error_permille: int = 100, **rules):
+    """trim_plan(**rules) and select_columns with its plan in sequence: -> (RecordColumns of the trimmed, kept records, stats).
+    adapters (see adapter_plan): between the two, adapter_plan narrows the trim plan -- the quality trim first, the adapter second,
+    the order of cutadapt and fastp -- with the same min_length; stats is then the trim plan's dict plus a key "adapter" that holds
+    the adapter plan's dict, and the number of records that come out is stats["adapter"]["records_kept"].  max_n and
+    min_mean_quality were judged on the range before the adapter cut."""
+    if adapters is not None:
+        codes = _adapter_codes(adapters)
     begin, end, keep, stats = trim_plan(handle, cols, **rules)
+    if adapters is not None:
+        begin, end, keep, a_stats = adapter_plan(handle, cols, codes, begin, end, keep, adapter_min_overlap, adapter_max_error_permille,
+                                                 rules.get("min_length", 1))
+        stats = dict(stats, adapter=a_stats)
     return select_columns(handle, cols, begin, end, keep, titles=titles), stats

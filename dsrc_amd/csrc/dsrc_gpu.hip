@@ -47,6 +47,7 @@
 #include "k_columns.h"
 #include "k_columns_enc.h"
 #include "k_columns_sel.h"
+#include "k_columns_adapt.h"
 
 namespace
 {
@@ -2215,14 +2216,14 @@ int sel_input_error(dsrcgpu_handle* h, u64 word)
 	return fail(h, DSRCGPU_E_INPUT, "columns: record %llu: %s", (unsigned long long)(word >> 4), why_sel[why - COLS_BEGIN_LOW]);
 }
 
-// col_in_args for the calls that may do without the titles
-int sel_in_args(dsrcgpu_handle* h, const dsrcgpu_columns_in* in, bool titles, ColIn& c)
+// col_in_args for the calls that may do without the titles (and, the adapter plan, without the qualities)
+int sel_in_args(dsrcgpu_handle* h, const dsrcgpu_columns_in* in, bool titles, ColIn& c, bool quals = true)
 {
 	if (!in) return fail(h, DSRCGPU_E_ARG, "null argument");
 	if (h->ds.color_space) return fail(h, DSRCGPU_E_ARG, "columns are defined for base space: a colour-space line is a primer plus colours");
 	if ((in->n_records | in->bases_len | (titles ? in->titles_len : 0)) >> 56) return fail(h, DSRCGPU_E_ARG, "columns: array lengths of 2^56 and more");
 	if (in->n_records && (!in->d_seq_offs || (titles && !in->d_title_offs))) return fail(h, DSRCGPU_E_ARG, "columns: null offset array");
-	if ((in->bases_len && (!in->d_bases || !in->d_quals)) || (titles && in->titles_len && !in->d_titles)) return fail(h, DSRCGPU_E_ARG, "columns: null array with a length");
+	if ((in->bases_len && (!in->d_bases || (quals && !in->d_quals))) || (titles && in->titles_len && !in->d_titles)) return fail(h, DSRCGPU_E_ARG, "columns: null array with a length");
 	c = ColIn{in->d_bases, in->d_quals, titles ? in->d_titles : nullptr, in->d_seq_offs, titles ? in->d_title_offs : nullptr, in->n_records, in->bases_len,
 	          titles ? in->titles_len : 0, h->ds.plus_repetition ? 1u : 0u, h->ds.quality_offset};
 	{
@@ -2315,6 +2316,62 @@ int dsrcgpu_columns_select_device(dsrcgpu_handle* h, const dsrcgpu_columns_in* i
 	hipLaunchKernelGGL(k_sel_apply, dim3(g_tiles), dim3(WG), 0, s, c, w, n_tiles, d_tiles, o, d_pos); KCHK();
 	hipLaunchKernelGGL(k_sel_gather, dim3((u32)std::max<u64>(1, std::min<u64>(4096, (c.n_recs + wpg - 1) / wpg))), dim3(WG), 0, s, c, w, o, d_pos); KCHK();
 	HIPCHK(hipStreamSynchronize(s));
+	return DSRCGPU_OK;
+}
+
+// the adapter search (k_columns_adapt.h): the rules are checked and turned into bit planes here, then the check pass and the planner run
+// back to back as in dsrcgpu_columns_trim_plan
+int dsrcgpu_columns_adapter_plan(dsrcgpu_handle* h, const dsrcgpu_columns_in* in, const dsrcgpu_adapter_rules* rules,
+								 const uint64_t* d_begin_in, const uint64_t* d_end_in, const uint8_t* d_keep_in,
+								 uint64_t* d_begin, uint64_t* d_end, uint8_t* d_keep, uint32_t* d_which, uint64_t stats[13])
+{
+	if (!h) return DSRCGPU_E_ARG;
+	if (!rules || !stats) return fail(h, DSRCGPU_E_ARG, "null argument");
+	for (u32 k = 0; k < 13; ++k) stats[k] = 0;
+	ColIn c;
+	{ const int rc = sel_in_args(h, in, false, c, false); if (rc) return rc; }
+	if (rules->n_adapters < 1 || rules->n_adapters > ADAPT_MAX) return fail(h, DSRCGPU_E_ARG, "adapter rules: n_adapters must be 1 .. 8");
+	AdaptRules R{};
+	R.k = rules->n_adapters; R.min_overlap = rules->min_overlap; R.permille = rules->max_error_permille; R.min_len = rules->min_length;
+	u32 shortest = 64;
+	for (u32 a = 0; a < ADAPT_MAX; ++a)
+	{
+		const u32 len = rules->adapter_len[a];
+		if (a >= R.k) { if (len) return fail(h, DSRCGPU_E_ARG, "adapter rules: a length behind n_adapters"); continue; }
+		if (len < 1 || len > 64) return fail(h, DSRCGPU_E_ARG, "adapter rules: adapter %u: a length of 1 .. 64 is needed", a);
+		shortest = std::min(shortest, len);
+		R.len[a] = len;
+		for (u32 j = 0; j < len; ++j)
+		{
+			const u32 code = rules->adapters[a][j];
+			if (code > 3) return fail(h, DSRCGPU_E_ARG, "adapter rules: adapter %u: code %u at position %u (A C G T = 0 .. 3 only)", a, code, j);
+			R.a0[a] |= (u64)(code & 1u) << j; R.a1[a] |= (u64)(code >> 1) << j;
+		}
+	}
+	if (rules->min_overlap < 1 || rules->min_overlap > shortest) return fail(h, DSRCGPU_E_ARG, "adapter rules: min_overlap must be 1 .. the shortest adapter's length");
+	if (rules->max_error_permille > 1000) return fail(h, DSRCGPU_E_ARG, "adapter rules: max_error_permille above 1000");
+	if (rules->reserved[0] | rules->reserved[1] | rules->reserved[2]) return fail(h, DSRCGPU_E_ARG, "adapter rules: reserved fields must be 0");
+	if (!d_begin_in != !d_end_in) return fail(h, DSRCGPU_E_ARG, "columns: d_begin_in and d_end_in go together");
+	if (c.n_recs == 0) return DSRCGPU_OK;
+	if (!d_begin || !d_end || !d_keep) return fail(h, DSRCGPU_E_ARG, "null argument");
+	HIPCHK(hipSetDevice(h->device));
+	hipStream_t s = h->stream;
+	{ const int rc = ensure_arena(h, 14 * 8 + 1024); if (rc) return rc; }
+	const size_t o_res = h->arena.alloc(14 * 8);
+	if (h->arena.failed) return fail(h, DSRCGPU_E_NOMEM, "arena exhausted (adapter plan)");
+	u64* d_res = AP<u64>(h, o_res);                      // error word, the thirteen statistics
+	HIPCHK(hipMemsetAsync(d_res, 0xFF, 8, s));
+	HIPCHK(hipMemsetAsync(d_res + 1, 0, 13 * 8, s));
+	const AdaptPlanIn w{d_begin_in, d_end_in, d_keep_in};
+	const u64 wpg = WG / 64;
+	hipLaunchKernelGGL(k_adapt_check, dim3((u32)std::max<u64>(1, std::min<u64>(1024, (c.n_recs + WG - 1) / WG))), dim3(WG), 0, s, c, w, d_res); KCHK();
+	hipLaunchKernelGGL(k_adapt_plan, dim3((u32)std::max<u64>(1, std::min<u64>(4096, (c.n_recs + wpg - 1) / wpg))), dim3(WG), 0, s, c, w, R, d_begin, d_end, d_keep, d_which,
+	                   d_res + 1, d_res); KCHK();
+	u64 res[14];
+	HIPCHK(hipMemcpyAsync(res, d_res, sizeof(res), hipMemcpyDeviceToHost, s));
+	HIPCHK(hipStreamSynchronize(s));
+	if (res[0] != COLE_NONE) return sel_input_error(h, res[0]);
+	for (u32 k = 0; k < 13; ++k) stats[k] = res[k + 1];
 	return DSRCGPU_OK;
 }
 

@@ -254,6 +254,51 @@ int dsrcgpu_columns_select_device(dsrcgpu_handle* h, const dsrcgpu_columns_in* i
 		const uint64_t* d_begin, const uint64_t* d_end, const uint8_t* d_keep,
 		const dsrcgpu_columns* out, uint64_t* d_source, uint64_t totals[3]);
 
+/* dsrcgpu_columns_adapter_plan: the second planner -- a 3' adapter search that takes a plan in and gives a narrower plan out, for
+ * dsrcgpu_columns_select_device to carry out.  Conventions as dsrcgpu_columns_trim_plan: the handle's own lane and stream, scratch
+ * from the arena, synchronised before it returns, codec state (fields capacity, a pending record layout) left alone, a colour-space
+ * handle: DSRCGPU_E_ARG.  Of `in` only d_bases and d_seq_offs are read; d_quals, d_titles and d_title_offs may be NULL.
+ * The plan in: d_begin_in / d_end_in (both NULL = whole reads, one without the other: DSRCGPU_E_ARG) and d_keep_in (NULL = every
+ * record; any non-zero byte keeps).  For record r with b = d_begin_in[r], e = d_end_in[r], n = e - b, x[i] = d_bases[b + i]:
+ *   for p = 0 .. n - 1, for a = 0 .. n_adapters - 1:           (the leftmost start position wins, at one p the lowest adapter index)
+ *     L = min(adapter_len[a], n - p)                           (the adapter may hang over the 3' end of the RANGE)
+ *     if L < min_overlap: next a
+ *     mm = the number of j < L with x[p + j] != adapters[a][j]  (a read code >= 4 -- N .. 255 -- matches nothing)
+ *     if mm * 1000 <= L * max_error_permille: found (p, a), stop
+ * Found: d_end[r] = b + p, d_which[r] = a; not found: d_end[r] = e, d_which[r] = 0xFFFFFFFF; d_begin[r] = b always; d_keep[r] = 1 iff
+ * the record came in kept and d_end[r] - d_begin[r] >= min_length, else 0.  A record that came in dropped is not searched: its range
+ * passes through, d_keep[r] = 0, d_which[r] = 0xFFFFFFFF, and it counts in no statistic.  Positions at or beyond e are outside the read
+ * whatever the array holds there (the next record, or a tail an earlier plan has cut).  d_which may be NULL.
+ * Not done here: indels, 5' and anchored adapters, IUPAC wildcards in the adapter, "best match" instead of leftmost, paired-end
+ * overlap detection, poly-G tails.
+ * stats (host): [0] records kept, [1] bases kept, [2] bases this call cut off kept records, [3] records in which an adapter was found
+ * (among those that came in kept), [4] records dropped for length, [5 + a] records in which adapter a was the one found.
+ * n_records == 0: DSRCGPU_OK, stats 0.
+ * DSRCGPU_E_ARG, nothing written: n_adapters 0 or above 8; a length of 0 or above 64, or a non-zero length behind n_adapters; an adapter
+ * code above 3; min_overlap 0 or above the shortest adapter's length; max_error_permille above 1000; a non-zero reserved field.
+ * DSRCGPU_E_INPUT (lowest record and reason in dsrcgpu_last_error, outputs untouched), for kept and dropped records alike: d_seq_offs
+ * out of order, a closing entry above bases_len, d_begin_in[r] < S[r], d_end_in[r] > S[r + 1], d_begin_in[r] > d_end_in[r].  No input
+ * makes a kernel read outside the caller's arrays.
+ * In place: each output array may be the very same pointer as its input counterpart (d_begin == d_begin_in, d_end == d_end_in, d_keep
+ * == d_keep_in): a record's three inputs are read before its outputs are written, and no other record's are touched.  In every other
+ * way the outputs must not overlap the inputs or the arrays of `in`; this is not checked. */
+typedef struct dsrcgpu_adapter_rules
+{
+	uint32_t n_adapters;            /* 1..8 */
+	uint32_t adapter_len[8];        /* 1..64 for the first n_adapters, 0 for the rest */
+	uint8_t  adapters[8][64];       /* host memory, base codes 0..3 (A C G T), 5' to 3' */
+	uint32_t min_overlap;           /* 1 .. the shortest adapter's length */
+	uint32_t max_error_permille;    /* 0..1000: mismatches allowed per 1000 compared bases */
+	uint32_t min_length;            /* keep a record iff it has at least this many bases in front of the adapter */
+	uint32_t reserved[3];           /* must be 0, else DSRCGPU_E_ARG */
+} dsrcgpu_adapter_rules;
+
+int dsrcgpu_columns_adapter_plan(dsrcgpu_handle* h, const dsrcgpu_columns_in* in, const dsrcgpu_adapter_rules* rules,
+		const uint64_t* d_begin_in, const uint64_t* d_end_in, const uint8_t* d_keep_in   /* device, may be NULL */,
+		uint64_t* d_begin, uint64_t* d_end, uint8_t* d_keep                              /* device, n_records each */,
+		uint32_t* d_which                                                                /* device, n_records, may be NULL */,
+		uint64_t stats[13]);
+
 /* Queue form of DsrcCompressor::Process (src/DsrcWorker.cpp:39-70):
  *   fastqQueue.Pop(partId, chunk)            -> dsrcgpu_submit(partId, chunk)      (bytes are copied into page-locked staging)
  *   ... Store ... dsrcQueue.Push(partId, blk) -> dsrcgpu_collect(&partId, &blk, ...)
