@@ -26,7 +26,7 @@ EXPORTS = [
     "dsrcgpu_chain_seed", "dsrcgpu_last_stage_timing", "dsrcgpu_try_collect", "dsrcgpu_prepare", "dsrcgpu_set_table_budget", "dsrcgpu_device_memory", "dsrcgpu_release_memory",
     "dsrcgpu_synth_fastq", "dsrcgpu_reserve_memory", "dsrcgpu_set_lanes", "dsrcgpu_submit_pinned",
     "dsrcgpu_decompress_batch_columns_device", "dsrcgpu_compress_columns_device", "dsrcgpu_columns_cut",
-    "dsrcgpu_columns_trim_plan", "dsrcgpu_columns_select_device", "dsrcgpu_columns_adapter_plan",
+    "dsrcgpu_columns_trim_plan", "dsrcgpu_columns_select_device", "dsrcgpu_columns_adapter_plan", "dsrcgpu_columns_pair_plan",
 ]
 
 # error codes of include/dsrc_gpu.h that callers tell apart (DsrcGpuError.code)
@@ -96,6 +96,24 @@ class AdapterRules(C.Structure):
 
 ADAPTER_STATS = ("records_kept", "bases_kept", "bases_cut", "records_trimmed", "dropped_length") + tuple("found_%d" % a for a in range(8))
 NO_ADAPTER = 0xFFFFFFFF          # d_which of a record in which none was found
+
+
+class PairRules(C.Structure):
+    """dsrcgpu_pair_rules: the figures of dsrcgpu_columns_pair_plan.  PairRules(min_overlap, max_mismatches, max_error_permille,
+    min_length); the library is the one that refuses figures out of range."""
+    _fields_ = [("min_overlap", C.c_uint32), ("max_mismatches", C.c_uint32), ("max_error_permille", C.c_uint32), ("min_length", C.c_uint32),
+                ("reserved", C.c_uint32 * 4)]
+
+    def __init__(self, min_overlap=30, max_mismatches=5, max_error_permille=200, min_length=1, reserved=(0, 0, 0, 0)):
+        super().__init__()
+        self.min_overlap, self.max_mismatches, self.max_error_permille, self.min_length = min_overlap, max_mismatches, max_error_permille, min_length
+        self.reserved = (C.c_uint32 * 4)(*reserved)
+
+
+PAIR_MAX_BASES = 1024            # DSRCGPU_PAIR_MAX_BASES: a pair with a longer range is not searched
+PAIR_STATS = ("pairs_kept", "bases_kept_1", "bases_kept_2", "bases_cut_1", "bases_cut_2", "overlap_found", "overlap_narrowed", "dropped_mate",
+              "dropped_length", "not_searched_long", "insert_sum")
+NO_INSERT = 0xFFFFFFFFFFFFFFFF   # d_insert of a pair in which no overlap was found
 
 
 class HostColumns(typing.NamedTuple):
@@ -432,6 +450,21 @@ class Handle:
         self._chk(self.L.dsrcgpu_columns_adapter_plan(self.h, C.byref(cols_in), C.byref(rules), C.c_void_p(d_begin_in), C.c_void_p(d_end_in),
                                                       C.c_void_p(d_keep_in), C.c_void_p(d_begin), C.c_void_p(d_end), C.c_void_p(d_keep),
                                                       C.c_void_p(d_which), stats))
+        return list(stats)
+
+    def columns_pair_plan(self, cols_in1: ColumnsIn, cols_in2: ColumnsIn, rules: PairRules, plan1_in, plan2_in, d_begin1: int, d_end1: int,
+                          d_begin2: int, d_end2: int, d_keep: int, d_insert=None):
+        """dsrcgpu_columns_pair_plan: the overlap search and the joint keep on the mates cols_in1 / cols_in2.  plan<s>_in is the triple
+        (d_begin_in, d_end_in, d_keep_in) of side s (device addresses or None: whole reads, every record); the ranges go out into
+        d_begin<s> / d_end<s> (uint64 each), the pair's flag into d_keep (uint8) and, if wanted, the insert size into d_insert (uint64,
+        NO_INSERT for none), all device memory of n_records entries; a range output may be the very array of its input, d_keep either
+        incoming keep.  Returns the eleven statistics (PAIR_STATS names them)."""
+        stats = (C.c_uint64 * 11)()
+        (b1, e1, k1), (b2, e2, k2) = plan1_in, plan2_in
+        self._chk(self.L.dsrcgpu_columns_pair_plan(self.h, C.byref(cols_in1), C.byref(cols_in2), C.byref(rules), C.c_void_p(b1), C.c_void_p(e1),
+                                                   C.c_void_p(k1), C.c_void_p(b2), C.c_void_p(e2), C.c_void_p(k2), C.c_void_p(d_begin1),
+                                                   C.c_void_p(d_end1), C.c_void_p(d_begin2), C.c_void_p(d_end2), C.c_void_p(d_keep),
+                                                   C.c_void_p(d_insert), stats))
         return list(stats)
 
     def columns_select_device(self, cols_in: ColumnsIn, d_begin, d_end, d_keep, out: Columns, d_source=None):

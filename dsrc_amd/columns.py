@@ -1,6 +1,7 @@
 """Records as torch tensors: decode_columns (dsrcgpu_decompress_batch_columns_device), the way back, encode_columns
 (dsrcgpu_compress_columns_device), and what runs between the two: trim_plan (dsrcgpu_columns_trim_plan), adapter_plan
-(dsrcgpu_columns_adapter_plan), select_columns (dsrcgpu_columns_select_device) and filter_columns, include/dsrc_gpu.h.
+(dsrcgpu_columns_adapter_plan), pair_plan (dsrcgpu_columns_pair_plan), select_columns (dsrcgpu_columns_select_device), filter_columns
+and, for paired-end data, filter_pairs, include/dsrc_gpu.h.
 
 The blocks are already in device memory; the arrays are allocated by torch on the same device and filled by the library's
 kernels -- no text, no host round trip of the payload.  With the emulator build of the library (tests/emu) device pointers
@@ -269,3 +270,93 @@ def filter_columns(handle: _lib.Handle, cols: RecordColumns, titles: bool = True
                                                  rules.get("min_length", 1))
         stats = dict(stats, adapter=a_stats)
     return select_columns(handle, cols, begin, end, keep, titles=titles), stats
+
+
+def _check_int(name, v, lo, hi):
+    if not isinstance(v, int) or isinstance(v, bool) or not lo <= v <= hi:
+        raise ValueError("%s must be an integer in %d..%d" % (name, lo, hi))
+
+
+def _check_pair_args(cols1, cols2, min_overlap, max_mismatches, max_error_permille, min_length):
+    _check_int("min_overlap", min_overlap, 1, _lib.PAIR_MAX_BASES)
+    _check_int("max_mismatches", max_mismatches, 0, 0xFFFFFFFF)
+    _check_int("max_error_permille", max_error_permille, 0, 1000)
+    _check_int("min_length", min_length, 0, 0xFFFFFFFF)
+    if cols1.n_records != cols2.n_records:
+        raise ValueError("the mates come in equal numbers: %d records of read 1, %d of read 2" % (cols1.n_records, cols2.n_records))
+    if cols1.bases.device != cols2.bases.device:
+        raise ValueError("both column sets live on one device")
+
+
+def pair_plan(handle: _lib.Handle, cols1: RecordColumns, cols2: RecordColumns, plan1=None, plan2=None, min_overlap: int = 30,
+              max_mismatches: int = 5, max_error_permille: int = 200, min_length: int = 1, return_insert: bool = False):
+    """dsrcgpu_columns_pair_plan on the mates cols1 / cols2 (record r of one is the mate of record r of the other): the overlap of
+    read 1 with the reverse complement of read 2 gives the insert size, each mate's 3' end is cut where the insert ends, and a pair is
+    kept iff both mates came in kept and both are still min_length bases long -> (begin1, end1, begin2, end2, keep, stats[, insert])
+    in fresh tensors.  plan1 / plan2: a (begin, end, keep) triple per side as trim_plan and adapter_plan return it (begin and end may
+    both be None, keep may be None), or None: whole reads, every record.  An overlap is accepted with at least min_overlap compared
+    bases, at most max_mismatches mismatches and at most max_error_permille of them per 1000 compared bases; forward shifts are tried
+    first, then read-through shifts, the first accepted one wins.  stats is a dict with the keys of _lib.PAIR_STATS; insert (int64)
+    is the insert size of the pair, -1 where no overlap was found.  Arguments out of range, and column sets of different record
+    counts or devices, raise ValueError before the library is called.  Nothing of the payload crosses to the host."""
+    _check_pair_args(cols1, cols2, min_overlap, max_mismatches, max_error_permille, min_length)
+    device = cols1.bases.device
+    R = cols1.n_records
+    plans = []
+    for plan in (plan1, plan2):
+        begin, end, keep = (None, None, None) if plan is None else plan
+        if (begin is None) != (end is None):
+            raise ValueError("begin and end go together")
+        if begin is not None:
+            begin = begin.to(torch.int64).contiguous(); end = end.to(torch.int64).contiguous()
+        if keep is not None:
+            keep = keep.to(torch.uint8).contiguous()
+        for t in (begin, end, keep):
+            if t is not None and (t.numel() != R or t.device != device):
+                raise ValueError("begin, end and keep have one entry per record, on the device of the columns")
+        plans.append((begin, end, keep))
+    cin1, held1 = _columns_in(cols1, titles=False)
+    cin2, held2 = _columns_in(cols2, titles=False)
+    adr = lambda t: None if t is None or not t.numel() else t.data_ptr()
+    i64 = dict(dtype=torch.int64, device=device)
+    out = [torch.empty(R, **i64) for _ in range(4)]
+    keep = torch.empty(R, dtype=torch.uint8, device=device)
+    insert = torch.empty(R, **i64) if return_insert else None
+    rules = _lib.PairRules(min_overlap, max_mismatches, max_error_permille, min_length)
+    _quiesce(device)
+    stats = handle.columns_pair_plan(cin1, cin2, rules, tuple(adr(t) for t in plans[0]), tuple(adr(t) for t in plans[1]),
+                                     out[0].data_ptr(), out[1].data_ptr(), out[2].data_ptr(), out[3].data_ptr(), keep.data_ptr(), adr(insert))
+    del held1, held2
+    got = (out[0], out[1], out[2], out[3], keep, dict(zip(_lib.PAIR_STATS, stats)))
+    return got + (insert,) if return_insert else got          # (2^64 - 1 read as int64 is -1)
+
+
+def filter_pairs(handle: _lib.Handle, cols1: RecordColumns, cols2: RecordColumns, titles: bool = True, adapters1=None, adapters2=None,
+                 overlap: bool = True, pair_min_overlap: int = 30, pair_max_mismatches: int = 5, pair_max_error_permille: int = 200,
+                 adapter_min_overlap: int = 3, adapter_max_error_permille: int = 100, **rules):
+    """filter_columns for paired-end data: per side trim_plan(**rules) and, if adapters<s> is given, adapter_plan; then pair_plan with
+    the same min_length, which cuts read-through found from the overlap of the mates and decides per PAIR; then one select_columns per
+    side with that side's ranges and the joint keep -> (out1, out2, stats), out1.n_records == out2.n_records always and record j of
+    one is the mate of record j of the other.  stats = {"read1": ..., "read2": ..., "pair": ...}: per side what filter_columns gives,
+    and the pair plan's dict.  overlap=False: no search, the joint keep is keep1 & keep2, no min_length is applied again, and "pair"
+    is absent."""
+    _check_pair_args(cols1, cols2, pair_min_overlap, pair_max_mismatches, pair_max_error_permille, rules.get("min_length", 1))
+    plans, stats = [], {}
+    codes1, codes2 = (_adapter_codes(a) if a is not None else None for a in (adapters1, adapters2))
+    for name, cols, codes in (("read1", cols1, codes1), ("read2", cols2, codes2)):
+        begin, end, keep, side = trim_plan(handle, cols, **rules)
+        if codes is not None:
+            begin, end, keep, a_stats = adapter_plan(handle, cols, codes, begin, end, keep, adapter_min_overlap, adapter_max_error_permille,
+                                                     rules.get("min_length", 1))
+            side = dict(side, adapter=a_stats)
+        plans.append((begin, end, keep)); stats[name] = side
+    if overlap:
+        b1, e1, b2, e2, keep, p_stats = pair_plan(handle, cols1, cols2, plans[0], plans[1], pair_min_overlap, pair_max_mismatches,
+                                                  pair_max_error_permille, rules.get("min_length", 1))
+        stats["pair"] = p_stats
+    else:
+        (b1, e1, k1), (b2, e2, k2) = plans
+        keep = ((k1 != 0) & (k2 != 0)).to(torch.uint8)
+    out1 = select_columns(handle, cols1, b1, e1, keep, titles=titles)
+    out2 = select_columns(handle, cols2, b2, e2, keep, titles=titles)
+    return out1, out2, stats

@@ -48,6 +48,7 @@
 #include "k_columns_enc.h"
 #include "k_columns_sel.h"
 #include "k_columns_adapt.h"
+#include "k_columns_pair.h"
 
 namespace
 {
@@ -2372,6 +2373,58 @@ int dsrcgpu_columns_adapter_plan(dsrcgpu_handle* h, const dsrcgpu_columns_in* in
 	HIPCHK(hipStreamSynchronize(s));
 	if (res[0] != COLE_NONE) return sel_input_error(h, res[0]);
 	for (u32 k = 0; k < 13; ++k) stats[k] = res[k + 1];
+	return DSRCGPU_OK;
+}
+
+// the pair plan (k_columns_pair.h): the check pass of the adapter plan once per side, each with an error word of its own (side 1 is
+// reported first), then the planner; the error words and the statistics come home in one copy
+int dsrcgpu_columns_pair_plan(dsrcgpu_handle* h, const dsrcgpu_columns_in* in1, const dsrcgpu_columns_in* in2, const dsrcgpu_pair_rules* rules,
+							  const uint64_t* d_begin1_in, const uint64_t* d_end1_in, const uint8_t* d_keep1_in,
+							  const uint64_t* d_begin2_in, const uint64_t* d_end2_in, const uint8_t* d_keep2_in,
+							  uint64_t* d_begin1, uint64_t* d_end1, uint64_t* d_begin2, uint64_t* d_end2, uint8_t* d_keep, uint64_t* d_insert,
+							  uint64_t stats[11])
+{
+	if (!h) return DSRCGPU_E_ARG;
+	if (!rules || !stats) return fail(h, DSRCGPU_E_ARG, "null argument");
+	for (u32 k = 0; k < PAIR_N_STATS; ++k) stats[k] = 0;
+	ColIn c1, c2;
+	{ const int rc = sel_in_args(h, in1, false, c1, false); if (rc) return rc; }
+	{ const int rc = sel_in_args(h, in2, false, c2, false); if (rc) return rc; }
+	if (c1.n_recs != c2.n_recs) return fail(h, DSRCGPU_E_ARG, "pair plan: %llu records of read 1, %llu of read 2", (unsigned long long)c1.n_recs, (unsigned long long)c2.n_recs);
+	if (rules->min_overlap < 1 || rules->min_overlap > DSRCGPU_PAIR_MAX_BASES) return fail(h, DSRCGPU_E_ARG, "pair rules: min_overlap must be 1 .. %u", (u32)DSRCGPU_PAIR_MAX_BASES);
+	if (rules->max_error_permille > 1000) return fail(h, DSRCGPU_E_ARG, "pair rules: max_error_permille above 1000");
+	if (rules->reserved[0] | rules->reserved[1] | rules->reserved[2] | rules->reserved[3]) return fail(h, DSRCGPU_E_ARG, "pair rules: reserved fields must be 0");
+	if (!d_begin1_in != !d_end1_in) return fail(h, DSRCGPU_E_ARG, "columns: d_begin1_in and d_end1_in go together");
+	if (!d_begin2_in != !d_end2_in) return fail(h, DSRCGPU_E_ARG, "columns: d_begin2_in and d_end2_in go together");
+	if (c1.n_recs == 0) return DSRCGPU_OK;
+	if (!d_begin1 || !d_end1 || !d_begin2 || !d_end2 || !d_keep) return fail(h, DSRCGPU_E_ARG, "null argument");
+	HIPCHK(hipSetDevice(h->device));
+	hipStream_t s = h->stream;
+	{ const int rc = ensure_arena(h, (2 + PAIR_N_STATS) * 8 + 1024); if (rc) return rc; }
+	const size_t o_res = h->arena.alloc((2 + PAIR_N_STATS) * 8);
+	if (h->arena.failed) return fail(h, DSRCGPU_E_NOMEM, "arena exhausted (pair plan)");
+	u64* d_res = AP<u64>(h, o_res);                      // an error word per side, the eleven statistics
+	HIPCHK(hipMemsetAsync(d_res, 0xFF, 2 * 8, s));
+	HIPCHK(hipMemsetAsync(d_res + 2, 0, PAIR_N_STATS * 8, s));
+	const AdaptPlanIn w1{d_begin1_in, d_end1_in, d_keep1_in}, w2{d_begin2_in, d_end2_in, d_keep2_in};
+	const PairRules R{rules->min_overlap, rules->max_mismatches, rules->max_error_permille, rules->min_length};
+	const PairOut o{d_begin1, d_end1, d_begin2, d_end2, d_keep, d_insert};
+	const u64 wpg = WG / 64;
+	const dim3 g_check((u32)std::max<u64>(1, std::min<u64>(1024, (c1.n_recs + WG - 1) / WG)));
+	hipLaunchKernelGGL(k_adapt_check, g_check, dim3(WG), 0, s, c1, w1, d_res); KCHK();
+	hipLaunchKernelGGL(k_adapt_check, g_check, dim3(WG), 0, s, c2, w2, d_res + 1); KCHK();
+	hipLaunchKernelGGL(k_pair_plan, dim3((u32)std::max<u64>(1, std::min<u64>(4096, (c1.n_recs + wpg - 1) / wpg))), dim3(WG), 0, s, c1, c2, w1, w2, R, o, d_res + 2, d_res); KCHK();
+	u64 res[2 + PAIR_N_STATS];
+	HIPCHK(hipMemcpyAsync(res, d_res, sizeof(res), hipMemcpyDeviceToHost, s));
+	HIPCHK(hipStreamSynchronize(s));
+	for (u32 side = 0; side < 2; ++side)
+		if (res[side] != COLE_NONE)
+		{
+			const int rc = sel_input_error(h, res[side]);
+			const std::string why = dsrcgpu_last_error(h);
+			return fail(h, rc, "pair plan, read %u: %s", side + 1, why.c_str());
+		}
+	for (u32 k = 0; k < PAIR_N_STATS; ++k) stats[k] = res[k + 2];
 	return DSRCGPU_OK;
 }
 

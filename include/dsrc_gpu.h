@@ -269,8 +269,8 @@ int dsrcgpu_columns_select_device(dsrcgpu_handle* h, const dsrcgpu_columns_in* i
  * the record came in kept and d_end[r] - d_begin[r] >= min_length, else 0.  A record that came in dropped is not searched: its range
  * passes through, d_keep[r] = 0, d_which[r] = 0xFFFFFFFF, and it counts in no statistic.  Positions at or beyond e are outside the read
  * whatever the array holds there (the next record, or a tail an earlier plan has cut).  d_which may be NULL.
- * Not done here: indels, 5' and anchored adapters, IUPAC wildcards in the adapter, "best match" instead of leftmost, paired-end
- * overlap detection, poly-G tails.
+ * Not done here: indels, 5' and anchored adapters, IUPAC wildcards in the adapter, "best match" instead of leftmost, poly-G tails.
+ * (Paired-end overlap detection: dsrcgpu_columns_pair_plan, below.)
  * stats (host): [0] records kept, [1] bases kept, [2] bases this call cut off kept records, [3] records in which an adapter was found
  * (among those that came in kept), [4] records dropped for length, [5 + a] records in which adapter a was the one found.
  * n_records == 0: DSRCGPU_OK, stats 0.
@@ -298,6 +298,65 @@ int dsrcgpu_columns_adapter_plan(dsrcgpu_handle* h, const dsrcgpu_columns_in* in
 		uint64_t* d_begin, uint64_t* d_end, uint8_t* d_keep                              /* device, n_records each */,
 		uint32_t* d_which                                                                /* device, n_records, may be NULL */,
 		uint64_t stats[13]);
+
+/* dsrcgpu_columns_pair_plan: the third planner, for paired-end data -- two column sets of equally many records, record r of `in2` is
+ * the mate of record r of `in1`.  It takes a plan in per side and gives a narrower plan out per side and ONE keep flag per pair, so
+ * that two dsrcgpu_columns_select_device calls with that flag keep the two outputs in step.  Read-through is found from the pair
+ * itself: where the insert is shorter than the reads, the reverse complement of read 2 overlaps read 1 at a shift that gives the insert
+ * size, and the 3' end of each mate is cut where the insert ends -- adapter remnants of any length, no adapter sequence needed.
+ * Conventions as dsrcgpu_columns_adapter_plan: the handle's own lane and stream, a few words of the arena, synchronised before it
+ * returns, codec state left alone, a colour-space handle: DSRCGPU_E_ARG.  Of each side only d_bases and d_seq_offs are read; d_quals,
+ * d_titles and d_title_offs may be NULL.  The plans in: d_begin<s>_in / d_end<s>_in (both NULL = whole reads; one without the other:
+ * DSRCGPU_E_ARG; the two sides are independent of each other) and d_keep<s>_in (NULL = every record; any non-zero byte keeps).
+ * For pair r, side s in {1, 2}: [b_s, e_s) its range in its own d_bases, S_s its record start, f_s = b_s - S_s (what an earlier plan cut
+ * off the 5' end), n_s = e_s - b_s; x[i] = bases1[b1 + i], y[j] = comp(bases2[e2 - 1 - j]) (the reverse complement of read 2's range),
+ * comp(c) = 3 - c for codes 0..3 (A C G T); a code >= 4 on either side matches nothing, not even itself.
+ *   for d in 0, 1, .., n1 - 1, then -1, -2, .., -(n2 - 1):               (the first accepted d wins; fastp's candidate order)
+ *     d >= 0: L = min(n1 - d, n2), compare x[d + i] with y[i]     for i < L
+ *     d <  0: L = min(n1, n2 + d), compare x[i]     with y[i - d] for i < L
+ *     if L < min_overlap: next d
+ *     mm = the number of i < L at which the two differ or either code is >= 4
+ *     if mm <= max_mismatches and mm * 1000 <= L * max_error_permille: found d, stop
+ * Found: the insert size is I = d + n2 + f1 + f2, the new lengths are n1' = min(n1, I - f1) and n2' = min(n2, I - f2) (d + n2 >= 1 always,
+ * so both are at least 1): d_end<s>[r] = b_s + n_s'; d_begin<s>[r] = b_s always; d_insert[r] = I.  Not found: both ranges unchanged,
+ * d_insert[r] = 2^64 - 1.  d_insert may be NULL.
+ * A pair is searched iff both mates came in kept and n1, n2 <= DSRCGPU_PAIR_MAX_BASES; a pair with a longer range is not searched and
+ * counted as such, its ranges pass through and the keep rule still applies to it.  d_keep[r] = 1 iff both mates came in kept and n1' >=
+ * min_length and n2' >= min_length.  A pair that came in with a mate dropped passes its ranges through with d_keep[r] = 0; if exactly one
+ * mate had been kept it counts in "dropped for the mate", if neither, in nothing.
+ * Not done here: indels, base correction in the overlap, merging the mates into one read, a check that the mates' titles agree,
+ * interleaved input, the "best" overlap instead of the first accepted one.
+ * stats (host): [0] pairs kept, [1] / [2] bases kept of read 1 / read 2, [3] / [4] bases this call cut off read 1 / read 2 of kept pairs,
+ * [5] pairs in which an overlap was found, [6] of those, pairs in which either range became shorter, [7] pairs dropped for the mate,
+ * [8] pairs dropped for length (both mates came in kept), [9] pairs not searched for a range above DSRCGPU_PAIR_MAX_BASES, [10] the sum
+ * of I over the pairs of [5].
+ * n_records == 0: DSRCGPU_OK, stats 0.
+ * DSRCGPU_E_ARG, nothing written: in1->n_records != in2->n_records; min_overlap 0 or above DSRCGPU_PAIR_MAX_BASES; max_error_permille
+ * above 1000; a non-zero reserved field; a half-given range pair; a null output other than d_insert.
+ * DSRCGPU_E_INPUT (outputs untouched), for kept and dropped records alike: the conditions of dsrcgpu_columns_adapter_plan on either
+ * side; dsrcgpu_last_error names the side (read 1 is reported first), the lowest record of that side and the reason.  No input makes a
+ * kernel read outside the caller's arrays.
+ * In place: each of the four range outputs may be the very pointer of its input counterpart, and d_keep may be d_keep1_in or
+ * d_keep2_in: a pair's inputs are all read before any of its outputs are written, and no other pair's are touched.  In every other way
+ * the outputs must not overlap the inputs or the arrays of `in1` / `in2`; this is not checked. */
+#define DSRCGPU_PAIR_MAX_BASES 1024
+typedef struct dsrcgpu_pair_rules
+{
+	uint32_t min_overlap;           /* 1 .. DSRCGPU_PAIR_MAX_BASES */
+	uint32_t max_mismatches;
+	uint32_t max_error_permille;    /* 0 .. 1000 */
+	uint32_t min_length;
+	uint32_t reserved[4];           /* must be 0 */
+} dsrcgpu_pair_rules;
+
+int dsrcgpu_columns_pair_plan(dsrcgpu_handle* h, const dsrcgpu_columns_in* in1, const dsrcgpu_columns_in* in2,
+		const dsrcgpu_pair_rules* rules,
+		const uint64_t* d_begin1_in, const uint64_t* d_end1_in, const uint8_t* d_keep1_in   /* device, may be NULL */,
+		const uint64_t* d_begin2_in, const uint64_t* d_end2_in, const uint8_t* d_keep2_in,
+		uint64_t* d_begin1, uint64_t* d_end1, uint64_t* d_begin2, uint64_t* d_end2          /* device, n_records each */,
+		uint8_t* d_keep                                                                     /* device, n_records: the pair's flag */,
+		uint64_t* d_insert                                                                  /* device, n_records, may be NULL */,
+		uint64_t stats[11]);
 
 /* Queue form of DsrcCompressor::Process (src/DsrcWorker.cpp:39-70):
  *   fastqQueue.Pop(partId, chunk)            -> dsrcgpu_submit(partId, chunk)      (bytes are copied into page-locked staging)
