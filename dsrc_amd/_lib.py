@@ -27,6 +27,7 @@ EXPORTS = [
     "dsrcgpu_synth_fastq", "dsrcgpu_reserve_memory", "dsrcgpu_set_lanes", "dsrcgpu_submit_pinned",
     "dsrcgpu_decompress_batch_columns_device", "dsrcgpu_compress_columns_device", "dsrcgpu_columns_cut",
     "dsrcgpu_columns_trim_plan", "dsrcgpu_columns_select_device", "dsrcgpu_columns_adapter_plan", "dsrcgpu_columns_pair_plan",
+    "dsrcgpu_columns_profile",
 ]
 
 # error codes of include/dsrc_gpu.h that callers tell apart (DsrcGpuError.code)
@@ -114,6 +115,25 @@ PAIR_MAX_BASES = 1024            # DSRCGPU_PAIR_MAX_BASES: a pair with a longer 
 PAIR_STATS = ("pairs_kept", "bases_kept_1", "bases_kept_2", "bases_cut_1", "bases_cut_2", "overlap_found", "overlap_narrowed", "dropped_mate",
               "dropped_length", "not_searched_long", "insert_sum")
 NO_INSERT = 0xFFFFFFFFFFFFFFFF   # d_insert of a pair in which no overlap was found
+
+
+class ProfileRules(C.Structure):
+    """dsrcgpu_profile_rules: ProfileRules(n_cycles, accumulate); the library is the one that refuses figures out of range."""
+    _fields_ = [("n_cycles", C.c_uint32), ("accumulate", C.c_uint32), ("reserved", C.c_uint32 * 6)]
+
+    def __init__(self, n_cycles=1, accumulate=0, reserved=(0, 0, 0, 0, 0, 0)):
+        super().__init__()
+        self.n_cycles, self.accumulate = n_cycles, accumulate
+        self.reserved = (C.c_uint32 * 6)(*reserved)
+
+
+PROFILE_MAX_CYCLES = 1024        # DSRCGPU_PROFILE_MAX_CYCLES
+PROFILE_TOTALS = ("records", "bases", "bases_q20", "bases_q30", "quality_sum", "gc_bases", "other_bases", "empty_records")
+
+
+def profile_words(n_cycles: int) -> int:
+    """DSRCGPU_PROFILE_WORDS: the uint64 words of a profile of n_cycles cycles."""
+    return 11 * n_cycles + 622
 
 
 class HostColumns(typing.NamedTuple):
@@ -466,6 +486,15 @@ class Handle:
                                                    C.c_void_p(d_end1), C.c_void_p(d_begin2), C.c_void_p(d_end2), C.c_void_p(d_keep),
                                                    C.c_void_p(d_insert), stats))
         return list(stats)
+
+    def columns_profile(self, cols_in: ColumnsIn, d_begin, d_end, d_keep, rules: ProfileRules, d_profile: int):
+        """dsrcgpu_columns_profile: the per-cycle profile of the records of `cols_in` under the plan d_begin / d_end / d_keep (device
+        addresses or None: whole reads, every record) into d_profile (device memory of profile_words(rules.n_cycles) uint64 words;
+        overwritten, or added to with rules.accumulate = 1).  Returns this call's own eight totals (PROFILE_TOTALS names them)."""
+        totals = (C.c_uint64 * 8)()
+        self._chk(self.L.dsrcgpu_columns_profile(self.h, C.byref(cols_in), C.c_void_p(d_begin), C.c_void_p(d_end), C.c_void_p(d_keep),
+                                                 C.byref(rules), C.c_void_p(d_profile), totals))
+        return list(totals)
 
     def columns_select_device(self, cols_in: ColumnsIn, d_begin, d_end, d_keep, out: Columns, d_source=None):
         """dsrcgpu_columns_select_device: the kept records of `cols_in`, cut to [begin, end), compacted into the device arrays `out`

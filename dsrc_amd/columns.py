@@ -1,7 +1,8 @@
 """Records as torch tensors: decode_columns (dsrcgpu_decompress_batch_columns_device), the way back, encode_columns
 (dsrcgpu_compress_columns_device), and what runs between the two: trim_plan (dsrcgpu_columns_trim_plan), adapter_plan
 (dsrcgpu_columns_adapter_plan), pair_plan (dsrcgpu_columns_pair_plan), select_columns (dsrcgpu_columns_select_device), filter_columns
-and, for paired-end data, filter_pairs, include/dsrc_gpu.h.
+and, for paired-end data, filter_pairs, and the report on either side of them, profile_columns (dsrcgpu_columns_profile),
+include/dsrc_gpu.h.
 
 The blocks are already in device memory; the arrays are allocated by torch on the same device and filled by the library's
 kernels -- no text, no host round trip of the payload.  With the emulator build of the library (tests/emu) device pointers
@@ -255,13 +256,96 @@ def adapter_plan(handle: _lib.Handle, cols: RecordColumns, adapters, begin=None,
     return got + (which.to(torch.int64),) if return_which else got
 
 
+@dataclasses.dataclass
+class ColumnsProfile:
+    """A profile of dsrcgpu_columns_profile: one int64 tensor of _lib.profile_words(n_cycles) counts on the device of the columns
+    (layout: include/dsrc_gpu.h) and views of its tables.  Nothing is copied but by summary()."""
+    data: torch.Tensor
+    n_cycles: int
+
+    def _table(self, offset, count):
+        return self.data[offset: offset + count]
+
+    @property
+    def totals(self):                  # 8, named by _lib.PROFILE_TOTALS
+        return self._table(0, 8)
+
+    @property
+    def base_by_cycle(self):           # n_cycles x 5: A, C, G, T, anything else
+        return self._table(8, 5 * self.n_cycles).view(self.n_cycles, 5)
+
+    @property
+    def quality_sum_by_cycle(self):    # n_cycles x 5
+        return self._table(8 + 5 * self.n_cycles, 5 * self.n_cycles).view(self.n_cycles, 5)
+
+    @property
+    def quality_hist(self):            # 256
+        return self._table(8 + 10 * self.n_cycles, 256)
+
+    @property
+    def length_hist(self):             # n_cycles + 1: the last bin holds the ranges of n_cycles bases and more
+        return self._table(264 + 10 * self.n_cycles, self.n_cycles + 1)
+
+    @property
+    def gc_hist(self):                 # 101: percent G or C among A C G T
+        return self._table(265 + 11 * self.n_cycles, 101)
+
+    @property
+    def mean_quality_hist(self):       # 256
+        return self._table(366 + 11 * self.n_cycles, 256)
+
+    def summary(self) -> dict:
+        """The eight totals as a dict of ints -- the only part that crosses to the host."""
+        return dict(zip(_lib.PROFILE_TOTALS, self.totals.tolist()))
+
+
+def profile_columns(handle: _lib.Handle, cols: RecordColumns, begin=None, end=None, keep=None, n_cycles=None, into=None) -> ColumnsProfile:
+    """dsrcgpu_columns_profile on the records of `cols` under the plan begin / end / keep (None: whole reads, every record; as the
+    planners return them) -> ColumnsProfile.  The cycle of a base is its position in the RANGE; positions from n_cycles - 1 on fold
+    into the last cycle.  n_cycles=None: the longest stored read, clipped to 1 .. _lib.PROFILE_MAX_CYCLES (that of `into` if given).
+    into: an earlier ColumnsProfile of the same n_cycles on the same device -- the counts are added to its tensor and it is returned,
+    so that the batches of a file sum to the profile of the file.  The profile of a plan equals the profile of select_columns with that
+    plan and needs no select.  Arguments out of range raise ValueError before the library is called.  Nothing of the payload crosses
+    to the host."""
+    device = cols.bases.device
+    R = cols.n_records
+    if into is not None:
+        if not isinstance(into, ColumnsProfile) or n_cycles not in (None, into.n_cycles):
+            raise ValueError("into is an earlier ColumnsProfile with the same n_cycles")
+        n_cycles = into.n_cycles
+    if n_cycles is None:
+        n_cycles = min(max(int(cols.seq_offsets.diff().max()), 1), _lib.PROFILE_MAX_CYCLES) if R else 1
+    _check_int("n_cycles", n_cycles, 1, _lib.PROFILE_MAX_CYCLES)
+    words = _lib.profile_words(n_cycles)
+    if into is not None and (into.data.dtype != torch.int64 or into.data.numel() != words or into.data.device != device or not into.data.is_contiguous()):
+        raise ValueError("into holds %d int64 counts on the device of the columns" % words)
+    if (begin is None) != (end is None):
+        raise ValueError("begin and end go together")
+    if begin is not None:
+        begin = begin.to(torch.int64).contiguous(); end = end.to(torch.int64).contiguous()
+    if keep is not None:
+        keep = keep.to(torch.uint8).contiguous()
+    for t in (begin, end, keep):
+        if t is not None and (t.numel() != R or t.device != device):
+            raise ValueError("begin, end and keep have one entry per record, on the device of the columns")
+    cin, held = _columns_in(cols, titles=False)
+    adr = lambda t: None if t is None or not t.numel() else t.data_ptr()
+    out = into if into is not None else ColumnsProfile(torch.empty(words, dtype=torch.int64, device=device), n_cycles)
+    _quiesce(device)
+    handle.columns_profile(cin, adr(begin), adr(end), adr(keep), _lib.ProfileRules(n_cycles, 1 if into is not None else 0), out.data.data_ptr())
+    del held
+    return out
+
+
 def filter_columns(handle: _lib.Handle, cols: RecordColumns, titles: bool = True, adapters=None, adapter_min_overlap: int = 3,
-                   adapter_max_error_permille: int = 100, **rules):
+                   adapter_max_error_permille: int = 100, profile: bool = False, **rules):
     """trim_plan(**rules) and select_columns with its plan in sequence: -> (RecordColumns of the trimmed, kept records, stats).
     adapters (see adapter_plan): between the two, adapter_plan narrows the trim plan -- the quality trim first, the adapter second,
     the order of cutadapt and fastp -- with the same min_length; stats is then the trim plan's dict plus a key "adapter" that holds
     the adapter plan's dict, and the number of records that come out is stats["adapter"]["records_kept"].  max_n and
-    min_mean_quality were judged on the range before the adapter cut."""
+    min_mean_quality were judged on the range before the adapter cut.
+    profile=True: stats gets "profile_before", the ColumnsProfile of `cols` as they came, and "profile_after", that of the records
+    that come out -- taken from the final plan on `cols`, with the same n_cycles."""
     if adapters is not None:
         codes = _adapter_codes(adapters)
     begin, end, keep, stats = trim_plan(handle, cols, **rules)
@@ -269,6 +353,9 @@ def filter_columns(handle: _lib.Handle, cols: RecordColumns, titles: bool = True
         begin, end, keep, a_stats = adapter_plan(handle, cols, codes, begin, end, keep, adapter_min_overlap, adapter_max_error_permille,
                                                  rules.get("min_length", 1))
         stats = dict(stats, adapter=a_stats)
+    if profile:
+        before = profile_columns(handle, cols)
+        stats = dict(stats, profile_before=before, profile_after=profile_columns(handle, cols, begin, end, keep, n_cycles=before.n_cycles))
     return select_columns(handle, cols, begin, end, keep, titles=titles), stats
 
 
@@ -333,13 +420,14 @@ def pair_plan(handle: _lib.Handle, cols1: RecordColumns, cols2: RecordColumns, p
 
 def filter_pairs(handle: _lib.Handle, cols1: RecordColumns, cols2: RecordColumns, titles: bool = True, adapters1=None, adapters2=None,
                  overlap: bool = True, pair_min_overlap: int = 30, pair_max_mismatches: int = 5, pair_max_error_permille: int = 200,
-                 adapter_min_overlap: int = 3, adapter_max_error_permille: int = 100, **rules):
+                 adapter_min_overlap: int = 3, adapter_max_error_permille: int = 100, profile: bool = False, **rules):
     """filter_columns for paired-end data: per side trim_plan(**rules) and, if adapters<s> is given, adapter_plan; then pair_plan with
     the same min_length, which cuts read-through found from the overlap of the mates and decides per PAIR; then one select_columns per
     side with that side's ranges and the joint keep -> (out1, out2, stats), out1.n_records == out2.n_records always and record j of
     one is the mate of record j of the other.  stats = {"read1": ..., "read2": ..., "pair": ...}: per side what filter_columns gives,
     and the pair plan's dict.  overlap=False: no search, the joint keep is keep1 & keep2, no min_length is applied again, and "pair"
-    is absent."""
+    is absent.  profile=True: stats["read1"] and stats["read2"] get "profile_before" and "profile_after" as in filter_columns, the
+    latter from that side's final ranges and the joint keep."""
     _check_pair_args(cols1, cols2, pair_min_overlap, pair_max_mismatches, pair_max_error_permille, rules.get("min_length", 1))
     plans, stats = [], {}
     codes1, codes2 = (_adapter_codes(a) if a is not None else None for a in (adapters1, adapters2))
@@ -357,6 +445,10 @@ def filter_pairs(handle: _lib.Handle, cols1: RecordColumns, cols2: RecordColumns
     else:
         (b1, e1, k1), (b2, e2, k2) = plans
         keep = ((k1 != 0) & (k2 != 0)).to(torch.uint8)
+    if profile:
+        for name, cols, b, e in (("read1", cols1, b1, e1), ("read2", cols2, b2, e2)):
+            before = profile_columns(handle, cols)
+            stats[name] = dict(stats[name], profile_before=before, profile_after=profile_columns(handle, cols, b, e, keep, n_cycles=before.n_cycles))
     out1 = select_columns(handle, cols1, b1, e1, keep, titles=titles)
     out2 = select_columns(handle, cols2, b2, e2, keep, titles=titles)
     return out1, out2, stats

@@ -49,6 +49,7 @@
 #include "k_columns_sel.h"
 #include "k_columns_adapt.h"
 #include "k_columns_pair.h"
+#include "k_columns_profile.h"
 
 namespace
 {
@@ -2425,6 +2426,51 @@ int dsrcgpu_columns_pair_plan(dsrcgpu_handle* h, const dsrcgpu_columns_in* in1, 
 			return fail(h, rc, "pair plan, read %u: %s", side + 1, why.c_str());
 		}
 	for (u32 k = 0; k < PAIR_N_STATS; ++k) stats[k] = res[k + 2];
+	return DSRCGPU_OK;
+}
+
+// the profile (k_columns_profile.h): the check pass of the adapter plan, then this call's profile is built in zeroed arena scratch and a
+// small kernel stores it into the caller's array or adds it there -- both do nothing unless the error word is clean, so d_profile is
+// untouched on an input error; the error word and the totals (the first eight words of the scratch) come home in one copy
+int dsrcgpu_columns_profile(dsrcgpu_handle* h, const dsrcgpu_columns_in* in, const uint64_t* d_begin, const uint64_t* d_end, const uint8_t* d_keep,
+							const dsrcgpu_profile_rules* rules, uint64_t* d_profile, uint64_t totals[8])
+{
+	if (!h) return DSRCGPU_E_ARG;
+	if (!rules || !totals || !d_profile) return fail(h, DSRCGPU_E_ARG, "null argument");
+	for (u32 k = 0; k < PROF_N_TOTALS; ++k) totals[k] = 0;
+	ColIn c;
+	{ const int rc = sel_in_args(h, in, false, c); if (rc) return rc; }
+	if (rules->n_cycles < 1 || rules->n_cycles > DSRCGPU_PROFILE_MAX_CYCLES) return fail(h, DSRCGPU_E_ARG, "profile rules: n_cycles must be 1 .. %u", (u32)DSRCGPU_PROFILE_MAX_CYCLES);
+	if (rules->accumulate > 1) return fail(h, DSRCGPU_E_ARG, "profile rules: accumulate must be 0 or 1");
+	for (u32 k = 0; k < 6; ++k)
+		if (rules->reserved[k]) return fail(h, DSRCGPU_E_ARG, "profile rules: reserved fields must be 0");
+	if (!d_begin != !d_end) return fail(h, DSRCGPU_E_ARG, "columns: d_begin and d_end go together");
+	const u32 C = rules->n_cycles, words = PROF_WORDS(C);
+	HIPCHK(hipSetDevice(h->device));
+	hipStream_t s = h->stream;
+	if (c.n_recs == 0)
+	{
+		if (!rules->accumulate) { HIPCHK(hipMemsetAsync(d_profile, 0, (size_t)words * 8, s)); HIPCHK(hipStreamSynchronize(s)); }
+		return DSRCGPU_OK;
+	}
+	{ const int rc = ensure_arena(h, (size_t)(words + 1) * 8 + 1024); if (rc) return rc; }
+	const size_t o_res = h->arena.alloc((size_t)(words + 1) * 8);
+	if (h->arena.failed) return fail(h, DSRCGPU_E_NOMEM, "arena exhausted (columns profile)");
+	u64* d_res = AP<u64>(h, o_res);                      // error word, this call's profile
+	HIPCHK(hipMemsetAsync(d_res, 0xFF, 8, s));
+	HIPCHK(hipMemsetAsync(d_res + 1, 0, (size_t)words * 8, s));
+	const AdaptPlanIn w{d_begin, d_end, d_keep};
+	const u64 wpg = WG / 64;
+	const dim3 grid((u32)std::max<u64>(1, std::min<u64>(prof_max_grid(C), (c.n_recs + wpg - 1) / wpg)));
+	hipLaunchKernelGGL(k_adapt_check, dim3((u32)std::max<u64>(1, std::min<u64>(1024, (c.n_recs + WG - 1) / WG))), dim3(WG), 0, s, c, w, d_res); KCHK();
+	if (C <= PROF_SMALL_CYCLES) { hipLaunchKernelGGL(k_prof<PROF_SMALL_CYCLES>, grid, dim3(WG), 0, s, c, w, C, d_res + 1, d_res); KCHK(); }
+	else { hipLaunchKernelGGL(k_prof<PROF_MAX_CYCLES>, grid, dim3(WG), 0, s, c, w, C, d_res + 1, d_res); KCHK(); }
+	hipLaunchKernelGGL(k_prof_store, dim3((words + WG - 1) / WG), dim3(WG), 0, s, d_res + 1, d_profile, words, rules->accumulate, d_res); KCHK();
+	u64 res[1 + PROF_N_TOTALS];
+	HIPCHK(hipMemcpyAsync(res, d_res, sizeof(res), hipMemcpyDeviceToHost, s));
+	HIPCHK(hipStreamSynchronize(s));
+	if (res[0] != COLE_NONE) return sel_input_error(h, res[0]);
+	for (u32 k = 0; k < PROF_N_TOTALS; ++k) totals[k] = res[k + 1];
 	return DSRCGPU_OK;
 }
 

@@ -358,6 +358,62 @@ int dsrcgpu_columns_pair_plan(dsrcgpu_handle* h, const dsrcgpu_columns_in* in1, 
 		uint64_t* d_insert                                                                  /* device, n_records, may be NULL */,
 		uint64_t stats[11]);
 
+/* dsrcgpu_columns_profile: the per-cycle quality report of the records of `in` under a plan -- what one reads to choose quality_3,
+ * min_length and the adapters, and to see what a filter did: the profile with no plan is "before", the profile of the same columns
+ * with the final plan is "after", and it needs no select.  Conventions as dsrcgpu_columns_adapter_plan: the handle's own lane and
+ * stream, scratch (one profile) from the arena, synchronised before it returns, codec state (fields capacity, a pending record layout)
+ * left alone, a colour-space handle: DSRCGPU_E_ARG.  Of `in`, d_bases, d_quals and d_seq_offs are read; d_titles and d_title_offs may
+ * be NULL.  The plan, as the planners give it: d_begin / d_end (both NULL = whole reads, one without the other: DSRCGPU_E_ARG) and
+ * d_keep (NULL = every record; any non-zero byte profiles the record; a record with a zero byte counts in nothing).
+ * With C = n_cycles, for every profiled record r with b = d_begin[r], e = d_end[r]:
+ *   n = e - b; qs = g = a = 0
+ *   for i = 0 .. n - 1:
+ *     x = d_bases[b + i]; q = d_quals[b + i]
+ *     k = x < 4 ? x : 4                           (the class: A, C, G, T or anything else)
+ *     c = min(i, C - 1)                           (the cycle is the position IN THE RANGE, not in the stored read; positions from C - 1
+ *                                                  on fold into the last cycle, so that every sum is conserved)
+ *     base[c][k] += 1; qsum[c][k] += q; qhist[q] += 1
+ *     tot[1] += 1; if q >= 20: tot[2] += 1; if q >= 30: tot[3] += 1; tot[4] += q
+ *     qs += q; if x == 1 or x == 2: g += 1, tot[5] += 1; if x < 4: a += 1, else tot[6] += 1
+ *   tot[0] += 1; len[min(n, C)] += 1
+ *   if a > 0: gc[100 * g / a] += 1                (integer division; a record without A C G T counts in no GC bin)
+ *   if n > 0: meanq[qs / n] += 1, else tot[7] += 1
+ * Positions at or beyond e are outside the read whatever the array holds there (the next record, or a tail a plan has cut).
+ * d_profile, in uint64 words (DSRCGPU_PROFILE_WORDS(C) of them):
+ *   0          tot[8]      [0] records profiled, [1] bases, [2] bases with q >= 20, [3] with q >= 30, [4] quality sum, [5] G or C bases,
+ *                          [6] bases of class 4, [7] profiled records with n = 0
+ *   8          base[C][5]
+ *   8 + 5C     qsum[C][5]
+ *   8 + 10C    qhist[256]
+ *   264 + 10C  len[C + 1]
+ *   265 + 11C  gc[101]
+ *   366 + 11C  meanq[256]
+ * accumulate == 0: d_profile is overwritten; 1: this call's counts are added to what it holds, so that the calls over the batches of a
+ * file give what one call on all of it gives.  totals (host) is this call's own tot[8] either way.  Everything is an integer sum: the
+ * result does not depend on the order in which the device takes the records and is bit-reproducible; no counter wraps below 2^64.
+ * n_records == 0: DSRCGPU_OK, totals 0, d_profile zeroed if accumulate == 0 and untouched otherwise.
+ * Not done here: k-mer counts, a duplication estimate, over-represented sequences, per-tile quality (nothing here reads the titles),
+ * a per-cycle quality HISTOGRAM (per cycle there is the sum and the count, so the mean, not the quartiles).
+ * On any error d_profile is untouched.  DSRCGPU_E_ARG: n_cycles 0 or above DSRCGPU_PROFILE_MAX_CYCLES; accumulate above 1; a non-zero
+ * reserved field; a half-given range pair; a null d_profile, rules or totals; a null in->d_quals (or d_bases) with bases_len > 0.
+ * DSRCGPU_E_INPUT (lowest record and reason in dsrcgpu_last_error), for kept and dropped records alike, exactly as
+ * dsrcgpu_columns_adapter_plan: d_seq_offs out of order, a closing entry above bases_len, d_begin[r] < S[r], d_end[r] > S[r + 1],
+ * d_begin[r] > d_end[r].  No input makes a kernel read outside the caller's arrays.  d_profile must not overlap the inputs. */
+#define DSRCGPU_PROFILE_MAX_CYCLES 1024
+#define DSRCGPU_PROFILE_WORDS(C) (11ull * (C) + 622)     /* uint64 words of a profile of C cycles */
+typedef struct dsrcgpu_profile_rules
+{
+	uint32_t n_cycles;      /* C: 1 .. DSRCGPU_PROFILE_MAX_CYCLES */
+	uint32_t accumulate;    /* 0: d_profile is overwritten; 1: this call's counts are ADDED to what d_profile holds */
+	uint32_t reserved[6];   /* must be 0 */
+} dsrcgpu_profile_rules;
+
+int dsrcgpu_columns_profile(dsrcgpu_handle* h, const dsrcgpu_columns_in* in,
+		const uint64_t* d_begin, const uint64_t* d_end, const uint8_t* d_keep   /* device, may be NULL: the plan, as the planners give it */,
+		const dsrcgpu_profile_rules* rules,
+		uint64_t* d_profile   /* device, DSRCGPU_PROFILE_WORDS(n_cycles) words */,
+		uint64_t totals[8]    /* host: this call's own contribution, whatever accumulate is */);
+
 /* Queue form of DsrcCompressor::Process (src/DsrcWorker.cpp:39-70):
  *   fastqQueue.Pop(partId, chunk)            -> dsrcgpu_submit(partId, chunk)      (bytes are copied into page-locked staging)
  *   ... Store ... dsrcQueue.Push(partId, blk) -> dsrcgpu_collect(&partId, &blk, ...)
