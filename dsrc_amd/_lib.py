@@ -608,6 +608,11 @@ class Handle:
         """Hands the batch arena and the table region back to the device (they are allocated again on demand)."""
         self._chk(self.L.dsrcgpu_release_memory(self.h))
 
+    def set_table_budget(self, nbytes: int):
+        """HBM a decoding pass of this handle may take for model tables (dsrcgpu_set_table_budget; 0 = automatic again).  A pass
+        whose tables do not fit runs in rounds; a budget below the largest table of a pass is raised to that table."""
+        self._chk(self.L.dsrcgpu_set_table_budget(self.h, C.c_uint64(nbytes)))
+
     def reserve_memory(self, arena_bytes, table_bytes=0):
         """Grows the batch arena / the decoder's table region to at least these sizes now (nothing shrinks)."""
         self._chk(self.L.dsrcgpu_reserve_memory(self.h, C.c_uint64(arena_bytes), C.c_uint64(table_bytes)))

@@ -1398,7 +1398,9 @@ int run_decode(dsrcgpu_handle* h, DecodeIO io)
 			region_words = sum;
 		}
 		if (d_rc) region_words = std::max<u64>(region_words, (u64)B * ((d_table_words(prm.dna_order, 0) + 31) & ~31ull));
-		u64 biggest = 0;
+		// the region holds the largest table of any kind the pass places: a budget below that table is raised to it (the 8-symbol DNA
+		// tables, known only after the quality stage, grow the region further down)
+		u64 biggest = d_rc ? (d_table_words(prm.dna_order, 0) + 31) & ~31ull : 0;
 		for (const DecTab& t : qtabs) biggest = std::max<u64>(biggest, (t.words + 31) & ~31ull);
 		region_words = std::max<u64>(std::min<u64>(region_words, budget_words), biggest);
 		if (region_words) { const int rc = ensure_dec_tables(h, region_words * 4); if (rc) return rc; }
@@ -1410,6 +1412,24 @@ int run_decode(dsrcgpu_handle* h, DecodeIO io)
 			const u32 gx = (u32)std::max<u64>(1, std::min<u64>(1024, mx / 4 / (256 * 4)));
 			hipLaunchKernelGGL(k_dec_fill, dim3(gx, r.count), dim3(256), 0, on, h->dec_tables, d_tabs + r.first);
 		};
+		// before a round is filled: every table of it lies inside the region (host arithmetic; a planning slip is an error code, not
+		// a write past the allocation)
+		auto round_fits = [&](const std::vector<DecTab>& tabs, const DecRound& r, const char* what) -> int
+		{
+			const u64 cap_words = h->dec_tables_cap / 4;
+			for (u32 i = 0; i < r.count; ++i)
+			{
+				const DecTab& t = tabs[r.first + i];
+				const u64 w = (t.words + 31) & ~31ull;
+				if (!h->dec_tables || t.off > cap_words || w > cap_words - t.off)
+					return fail(h, DSRCGPU_E_STATE, "block %u: the %s table of %llu words at word %llu does not fit the table region of %llu words", t.block, what, (unsigned long long)w, (unsigned long long)t.off, (unsigned long long)cap_words);
+			}
+			return DSRCGPU_OK;
+		};
+		// DSRC_GPU_DEBUG: what this pass did with the region (one line, below)
+		const u64 dbg_budget = budget_words * 4; u64 dbg_region = h->dec_tables_cap;
+		u32 dbg_qrounds = 0, dbg_r4 = 0, dbg_r8 = 0, dbg_b4 = 0, dbg_b8 = 0, dbg_plain = 0, dbg_n[5] = {0, 0, 0, 0, 0};
+		for (const DecTab& t : qtabs) for (u32 k = 0; k < 5; ++k) if (t.n == (8u << k)) ++dbg_n[k];
 		// Verification of blocks just written (io.hints): the DNA chains start at once, on the range-coder stream, next to the quality
 		// chains -- if the tables of both fit the region together (one round each); otherwise one stage after the other as for archives.
 		bool par = false;
@@ -1428,7 +1448,7 @@ int run_decode(dsrcgpu_handle* h, DecodeIO io)
 			{
 				const int rc = ensure_dec_tables(h, (qsum + dsum) * 4);
 				if (rc) return rc;
-				region_words = h->dec_tables_cap / 4;
+				region_words = h->dec_tables_cap / 4; dbg_region = h->dec_tables_cap;
 				u64 top = qsum;
 				for (DecTab& t : ptabs) { t.off = top; top += (t.words + 31) & ~31ull; }
 				par = true;
@@ -1439,6 +1459,9 @@ int run_decode(dsrcgpu_handle* h, DecodeIO io)
 				HIPCHK(hipEventRecord(h->ev[2], s));
 				HIPCHK(hipStreamWaitEvent(h->rc_stream, h->ev[2], 0));
 				const DecRound r4{0, p4}, r8{p4, (u32)ptabs.size() - p4};
+				{ const int rc4 = round_fits(ptabs, r4, "4-symbol DNA"); if (rc4) return rc4; }
+				{ const int rc8 = round_fits(ptabs, r8, "8-symbol DNA"); if (rc8) return rc8; }
+				dbg_r4 = r4.count ? 1 : 0; dbg_b4 = r4.count; dbg_r8 = r8.count ? 1 : 0; dbg_b8 = r8.count;
 				if (r4.count)
 				{
 					fill_round(d_tabs, ptabs, r4, h->rc_stream); KCHK();
@@ -1457,8 +1480,10 @@ int run_decode(dsrcgpu_handle* h, DecodeIO io)
 			const std::vector<DecRound> rounds = plan_rounds(qtabs, region_words);      // (with the DNA tables behind them: one round)
 			DecTab* d_tabs = AP<DecTab>(h, o_qtabs);
 			HIPCHK(hipMemcpyAsync(d_tabs, qtabs.data(), sizeof(DecTab) * qtabs.size(), hipMemcpyHostToDevice, s));
+			dbg_qrounds = (u32)rounds.size();
 			for (const DecRound& r : rounds)
 			{
+				{ const int rcq = round_fits(qtabs, r, "quality"); if (rcq) return rcq; }
 				fill_round(d_tabs, qtabs, r, s); KCHK();
 				// one launch per alphabet size the round contains
 				u32 sizes_present = 0;
@@ -1474,7 +1499,7 @@ int run_decode(dsrcgpu_handle* h, DecodeIO io)
 		if (par) HIPCHK(hipStreamWaitEvent(s, h->ev[3], 0));
 		hipLaunchKernelGGL(k_dec_dhead, dim3((B + 63) / 64), dim3(64), 0, s, io.d_in, d_desc, d_state, prm, par ? (const DecHint*)AP<DecHint>(h, o_hints) : (const DecHint*)nullptr); KCHK();
 		bool any_plain = !d_rc;
-		if (par) { for (u32 b = 0; b < B; ++b) if (io.hints[b].d_scheme == 255) any_plain = true; }
+		if (par) { for (u32 b = 0; b < B; ++b) if (io.hints[b].d_scheme == 255) { any_plain = true; ++dbg_plain; } }
 		if (d_rc && !par)
 		{
 			HIPCHK(hipMemcpyAsync(st.data(), d_state, sizeof(DecState) * B, hipMemcpyDeviceToHost, s));
@@ -1488,7 +1513,7 @@ int run_decode(dsrcgpu_handle* h, DecodeIO io)
 			{
 				for (u32 b = 0; b < B; ++b)
 				{
-					if (st[b].d_scheme == 255) { any_plain = true; continue; }
+					if (st[b].d_scheme == 255) { any_plain = true; dbg_plain += pass == 0; continue; }
 					if (st[b].d_scheme != pass) continue;
 					DecTab t; t.block = b; t.off = 0; t.n = 0; t.words = d_table_words(prm.dna_order, pass);
 					dtabs.push_back(t);
@@ -1506,19 +1531,26 @@ int run_decode(dsrcgpu_handle* h, DecodeIO io)
 			const std::vector<DecRound> r4 = plan_rounds(t4, region_words), r8 = plan_rounds(t8, region_words);
 			std::copy(t4.begin(), t4.end(), dtabs.begin()); std::copy(t8.begin(), t8.end(), dtabs.begin() + n4);
 			if (!dtabs.empty()) HIPCHK(hipMemcpyAsync(d_tabs, dtabs.data(), sizeof(DecTab) * dtabs.size(), hipMemcpyHostToDevice, s));
+			dbg_r4 = (u32)r4.size(); dbg_b4 = n4; dbg_r8 = (u32)r8.size(); dbg_b8 = (u32)dtabs.size() - n4;
 			for (const DecRound& r : r4)
 			{
+				{ const int rcd = round_fits(dtabs, r, "4-symbol DNA"); if (rcd) return rcd; }
 				fill_round(d_tabs, dtabs, r, s); KCHK();
 				hipLaunchKernelGGL(k_dec_dnarc<4>, dim3((r.count + 63) / 64), dim3(64), 0, s, io.d_in, d_desc, d_state, d_tabs + r.first, r.count, AP<u8>(h, o_d), h->dec_tables, prm); KCHK();
 			}
 			for (const DecRound& r8r : r8)
 			{
 				const DecRound r{r8r.first + n4, r8r.count};
+				{ const int rcd = round_fits(dtabs, r, "8-symbol DNA"); if (rcd) return rcd; }
 				fill_round(d_tabs, dtabs, r, s); KCHK();
 				hipLaunchKernelGGL(k_dec_dnarc<8>, dim3((r.count + 63) / 64), dim3(64), 0, s, io.d_in, d_desc, d_state, d_tabs + r.first, r.count, AP<u8>(h, o_d), h->dec_tables, prm); KCHK();
 			}
 		}
 		if (any_plain) { hipLaunchKernelGGL(k_dec_dna0, dim3(B), dim3(64), 0, s, io.d_in, d_desc, d_state, AP<u32>(h, o_nodes), AP<u8>(h, o_d), prm); KCHK(); }
+		if (getenv("DSRC_GPU_DEBUG"))
+			fprintf(stderr, "[dsrc_gpu] %p decode tables (%u blocks): budget %llu, region %llu, final %llu bytes; quality rounds %u, tables n8 %u n16 %u n32 %u n64 %u n128 %u; "
+			        "dna4 rounds %u blocks %u; dna8 rounds %u blocks %u; plain %u; par %d\n", (void*)h, B, (unsigned long long)dbg_budget, (unsigned long long)dbg_region,
+			        (unsigned long long)h->dec_tables_cap, dbg_qrounds, dbg_n[0], dbg_n[1], dbg_n[2], dbg_n[3], dbg_n[4], dbg_r4, dbg_b4, dbg_r8, dbg_b8, dbg_plain, par ? 1 : 0);
 	}
 	{
 		const u32 gx = std::max(1u, std::min(64u, (max_recs + 4 * WAVES - 1) / (4 * WAVES)));

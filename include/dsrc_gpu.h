@@ -487,7 +487,11 @@ int dsrcgpu_set_record_layout(dsrcgpu_handle* h, uint32_t n, const uint32_t* chu
 
 /* Decoding the order-context levels keeps one adaptive model table per block in flight (up to 64 MiB at -q2, DESIGN.md
  * section 11); by default a pass takes 70 % of the HBM that is free when it starts.  Hosts that run several decoding
- * handles on one device give each its share: dsrcgpu_set_table_budget(h, bytes) (0 = automatic again). */
+ * handles on one device give each its share: dsrcgpu_set_table_budget(h, bytes) (0 = automatic again).  A pass whose tables do
+ * not fit the budget decodes in rounds (as many tables as fit at a time, at least one).  A budget below the largest single table
+ * of a pass (2 MiB for a 4-symbol DNA table at -d3, 32 MiB for an 8-symbol one, up to 64 MiB for a quality table at -q2) is raised
+ * to that table: the region is never smaller than one table plus the allocation's slack of 1/16 + 4 KiB, and a region an
+ * earlier pass left larger is kept, not shrunk.  DSRC_GPU_DEBUG=1 prints the budget, the region and the rounds of every pass. */
 int dsrcgpu_set_table_budget(dsrcgpu_handle* h, uint64_t bytes);
 int dsrcgpu_device_memory(int device, uint64_t* free_bytes, uint64_t* total_bytes);
 /* A handle keeps its batch arena and its table region between calls (tens of GB after a large pass).  A host that moves on to
