@@ -27,7 +27,7 @@ EXPORTS = [
     "dsrcgpu_synth_fastq", "dsrcgpu_reserve_memory", "dsrcgpu_set_lanes", "dsrcgpu_submit_pinned",
     "dsrcgpu_decompress_batch_columns_device", "dsrcgpu_compress_columns_device", "dsrcgpu_columns_cut",
     "dsrcgpu_columns_trim_plan", "dsrcgpu_columns_select_device", "dsrcgpu_columns_adapter_plan", "dsrcgpu_columns_pair_plan",
-    "dsrcgpu_columns_profile",
+    "dsrcgpu_columns_profile", "dsrcgpu_columns_merge_device",
 ]
 
 # error codes of include/dsrc_gpu.h that callers tell apart (DsrcGpuError.code)
@@ -115,6 +115,22 @@ PAIR_MAX_BASES = 1024            # DSRCGPU_PAIR_MAX_BASES: a pair with a longer 
 PAIR_STATS = ("pairs_kept", "bases_kept_1", "bases_kept_2", "bases_cut_1", "bases_cut_2", "overlap_found", "overlap_narrowed", "dropped_mate",
               "dropped_length", "not_searched_long", "insert_sum")
 NO_INSERT = 0xFFFFFFFFFFFFFFFF   # d_insert of a pair in which no overlap was found
+
+
+class MergeRules(C.Structure):
+    """dsrcgpu_merge_rules: the figures of dsrcgpu_columns_merge_device.  MergeRules(min_overlap, max_mismatches, max_error_permille,
+    quality_cap); the library is the one that refuses figures out of range."""
+    _fields_ = [("min_overlap", C.c_uint32), ("max_mismatches", C.c_uint32), ("max_error_permille", C.c_uint32), ("quality_cap", C.c_uint32),
+                ("reserved", C.c_uint32 * 4)]
+
+    def __init__(self, min_overlap=30, max_mismatches=5, max_error_permille=200, quality_cap=41, reserved=(0, 0, 0, 0)):
+        super().__init__()
+        self.min_overlap, self.max_mismatches, self.max_error_permille, self.quality_cap = min_overlap, max_mismatches, max_error_permille, quality_cap
+        self.reserved = (C.c_uint32 * 4)(*reserved)
+
+
+MERGE_STATS = ("pairs_merged", "bases_written", "overlap_sum", "overlap_agree", "overlap_corrected", "overlap_one_sided", "overlap_neither",
+               "not_kept", "no_insert", "bad_geometry", "short_overlap", "over_budget")
 
 
 class ProfileRules(C.Structure):
@@ -486,6 +502,27 @@ class Handle:
                                                    C.c_void_p(d_end1), C.c_void_p(d_begin2), C.c_void_p(d_end2), C.c_void_p(d_keep),
                                                    C.c_void_p(d_insert), stats))
         return list(stats)
+
+    def columns_merge_device(self, cols_in1: ColumnsIn, cols_in2: ColumnsIn, rules: MergeRules, ranges1, ranges2, d_keep, d_insert, out: Columns,
+                             d_merged, d_source=None):
+        """dsrcgpu_columns_merge_device: the mates cols_in1 / cols_in2 whose ranges overlap by the insert sizes d_insert (uint64, as
+        columns_pair_plan wrote them) merged into one read each, compacted into the device arrays `out`.  ranges<s> is the pair
+        (d_begin, d_end) of side s (device addresses or None: whole reads), d_keep the pair's flag (or None: every pair); d_merged
+        (uint8, n_records) gets 1 for every pair that is in `out`, d_source (uint64, or None) the pair index of each output record.
+        Returns (totals, stats): records, bases, title bytes of `out`, and the twelve statistics (MERGE_STATS names them);
+        DsrcGpuError.code == E_CAPACITY when an array is too small -- `need` of the exception then holds the totals and `stats` the
+        statistics."""
+        totals, stats = (C.c_uint64 * 3)(), (C.c_uint64 * 12)()
+        (b1, e1), (b2, e2) = ranges1, ranges2
+        rc = self.L.dsrcgpu_columns_merge_device(self.h, C.byref(cols_in1), C.byref(cols_in2), C.byref(rules), C.c_void_p(b1), C.c_void_p(e1),
+                                                 C.c_void_p(b2), C.c_void_p(e2), C.c_void_p(d_keep), C.c_void_p(d_insert), C.byref(out),
+                                                 C.c_void_p(d_merged), C.c_void_p(d_source), totals, stats)
+        if rc < 0:
+            e = DsrcGpuError(rc, self.L.dsrcgpu_last_error(self.h).decode())
+            e.need = list(totals) if rc == E_CAPACITY else None
+            e.stats = list(stats) if rc == E_CAPACITY else None
+            raise e
+        return list(totals), list(stats)
 
     def columns_profile(self, cols_in: ColumnsIn, d_begin, d_end, d_keep, rules: ProfileRules, d_profile: int):
         """dsrcgpu_columns_profile: the per-cycle profile of the records of `cols_in` under the plan d_begin / d_end / d_keep (device

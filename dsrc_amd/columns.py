@@ -1,8 +1,8 @@
 """Records as torch tensors: decode_columns (dsrcgpu_decompress_batch_columns_device), the way back, encode_columns
 (dsrcgpu_compress_columns_device), and what runs between the two: trim_plan (dsrcgpu_columns_trim_plan), adapter_plan
-(dsrcgpu_columns_adapter_plan), pair_plan (dsrcgpu_columns_pair_plan), select_columns (dsrcgpu_columns_select_device), filter_columns
-and, for paired-end data, filter_pairs, and the report on either side of them, profile_columns (dsrcgpu_columns_profile),
-include/dsrc_gpu.h.
+(dsrcgpu_columns_adapter_plan), pair_plan (dsrcgpu_columns_pair_plan), merge_pairs (dsrcgpu_columns_merge_device), select_columns
+(dsrcgpu_columns_select_device), filter_columns and, for paired-end data, filter_pairs, and the report on either side of them,
+profile_columns (dsrcgpu_columns_profile), include/dsrc_gpu.h.
 
 The blocks are already in device memory; the arrays are allocated by torch on the same device and filled by the library's
 kernels -- no text, no host round trip of the payload.  With the emulator build of the library (tests/emu) device pointers
@@ -418,17 +418,93 @@ def pair_plan(handle: _lib.Handle, cols1: RecordColumns, cols2: RecordColumns, p
     return got + (insert,) if return_insert else got          # (2^64 - 1 read as int64 is -1)
 
 
+def merge_pairs(handle: _lib.Handle, cols1: RecordColumns, cols2: RecordColumns, begin1=None, end1=None, begin2=None, end2=None, keep=None,
+                insert=None, min_overlap: int = 30, max_mismatches: int = 5, max_error_permille: int = 200, quality_cap: int = 41,
+                titles: bool = True, return_source: bool = False):
+    """dsrcgpu_columns_merge_device on the mates cols1 / cols2 with what pair_plan(return_insert=True) gave: the ranges begin<s> /
+    end<s> (None: whole reads), the pair's keep (None: every pair) and `insert` (required; int64, -1 = no overlap found).  A kept pair
+    whose ranges overlap, at the place its insert size says, by at least min_overlap positions with at most max_mismatches mismatches
+    and at most max_error_permille of them per 1000 becomes ONE read: read 1, then the reverse complement of what read 2 adds, with a
+    consensus in the overlap -- equal bases sum their qualities up to max(quality_cap, q1, q2), different ones leave the better base
+    with the difference -- under read 1's title -> (RecordColumns of the merged reads, merged, stats[, source]): merged (uint8) is 1
+    for the pairs that are in the output, stats a dict with the keys of _lib.MERGE_STATS, source[j] (int64) the pair of output record j.
+    The unmerged mates are select_columns(..., keep=keep & ~merged) on either side.  The first library call sizes the arrays, the
+    second one fills them.  Arguments out of range, half-given ranges, mis-sized tensors and column sets of different record counts or
+    devices raise ValueError before the library is called.  Nothing of the payload crosses to the host."""
+    _check_int("min_overlap", min_overlap, 1, 0xFFFFFFFF)
+    _check_int("max_mismatches", max_mismatches, 0, 0xFFFFFFFF)
+    _check_int("max_error_permille", max_error_permille, 0, 1000)
+    _check_int("quality_cap", quality_cap, 0, 255)
+    if cols1.n_records != cols2.n_records:
+        raise ValueError("the mates come in equal numbers: %d records of read 1, %d of read 2" % (cols1.n_records, cols2.n_records))
+    if cols1.bases.device != cols2.bases.device:
+        raise ValueError("both column sets live on one device")
+    if insert is None:
+        raise ValueError("insert is needed: the insert sizes of pair_plan(..., return_insert=True)")
+    if (begin1 is None) != (end1 is None) or (begin2 is None) != (end2 is None):
+        raise ValueError("begin and end go together")
+    device = cols1.bases.device
+    R = cols1.n_records
+    i64s = [None if t is None else t.to(torch.int64).contiguous() for t in (begin1, end1, begin2, end2, insert)]
+    if keep is not None:
+        keep = keep.to(torch.uint8).contiguous()
+    for t in i64s + [keep]:
+        if t is not None and (t.numel() != R or t.device != device):
+            raise ValueError("begin, end, keep and insert have one entry per pair, on the device of the columns")
+    cin1, held1 = _columns_in(cols1, titles)
+    cin2, held2 = _columns_in(cols2, titles=False)
+    spare = held1[-1]
+    adr = lambda t: None if t is None or not t.numel() else t.data_ptr()
+    ptr = lambda t: t.data_ptr() if t.numel() else spare.data_ptr()
+    u8 = dict(dtype=torch.uint8, device=device); i64 = dict(dtype=torch.int64, device=device)
+    merged = torch.empty(R, **u8)
+    rules = _lib.MergeRules(min_overlap, max_mismatches, max_error_permille, quality_cap)
+    args = (cin1, cin2, rules, (adr(i64s[0]), adr(i64s[1])), (adr(i64s[2]), adr(i64s[3])), adr(keep), ptr(i64s[4]))
+    _quiesce(device)
+    need = [0, 0, 0]
+    try:
+        handle.columns_merge_device(*args, _lib.Columns(d_titles=spare.data_ptr() if titles else None), ptr(merged))
+    except _lib.DsrcGpuError as e:
+        if e.code != _lib.E_CAPACITY:
+            raise
+        need = e.need
+    K, S, T = need
+    bases = torch.empty(S, **u8); quals = torch.empty(S, **u8)
+    seq_offsets = torch.empty(K + 1, **i64)
+    title_bytes = torch.empty(T if titles else 0, **u8)
+    title_offsets = torch.empty(K + 1 if titles else 0, **i64)
+    source = torch.empty(K, **i64)
+    out = _lib.Columns(ptr(bases), S, ptr(quals), S, ptr(title_bytes) if titles else None, T if titles else 0,
+                       seq_offsets.data_ptr(), title_offsets.data_ptr() if titles else None, K)
+    _quiesce(device)
+    totals, stats = handle.columns_merge_device(*args, out, ptr(merged), adr(source) if return_source else None)
+    assert totals == need
+    del held1, held2
+    got = (RecordColumns(bases, quals, title_bytes, seq_offsets, title_offsets, torch.tensor([0, K], **i64)), merged, dict(zip(_lib.MERGE_STATS, stats)))
+    return got + (source,) if return_source else got
+
+
 def filter_pairs(handle: _lib.Handle, cols1: RecordColumns, cols2: RecordColumns, titles: bool = True, adapters1=None, adapters2=None,
                  overlap: bool = True, pair_min_overlap: int = 30, pair_max_mismatches: int = 5, pair_max_error_permille: int = 200,
-                 adapter_min_overlap: int = 3, adapter_max_error_permille: int = 100, profile: bool = False, **rules):
+                 adapter_min_overlap: int = 3, adapter_max_error_permille: int = 100, profile: bool = False, merge: bool = False,
+                 merge_quality_cap: int = 41, **rules):
     """filter_columns for paired-end data: per side trim_plan(**rules) and, if adapters<s> is given, adapter_plan; then pair_plan with
     the same min_length, which cuts read-through found from the overlap of the mates and decides per PAIR; then one select_columns per
     side with that side's ranges and the joint keep -> (out1, out2, stats), out1.n_records == out2.n_records always and record j of
     one is the mate of record j of the other.  stats = {"read1": ..., "read2": ..., "pair": ...}: per side what filter_columns gives,
     and the pair plan's dict.  overlap=False: no search, the joint keep is keep1 & keep2, no min_length is applied again, and "pair"
     is absent.  profile=True: stats["read1"] and stats["read2"] get "profile_before" and "profile_after" as in filter_columns, the
-    latter from that side's final ranges and the joint keep."""
+    latter from that side's final ranges and the joint keep.
+    merge=True (needs overlap=True): behind the pair plan, merge_pairs with the pair plan's ranges, keep and insert sizes, its
+    min_overlap, max_mismatches and max_error_permille, and merge_quality_cap turns the kept pairs whose mates overlap into one read
+    each; the two selects then take keep & ~merged -> (out1, out2, merged, stats): `merged` the RecordColumns of the merged reads,
+    out1 / out2 the mates of the kept pairs that were not merged, stats["merge"] the dict of merge_pairs; merged.n_records +
+    out1.n_records is the pair plan's pairs_kept, and "profile_after" is that of out1 / out2."""
     _check_pair_args(cols1, cols2, pair_min_overlap, pair_max_mismatches, pair_max_error_permille, rules.get("min_length", 1))
+    if merge:
+        if not overlap:
+            raise ValueError("merge=True needs overlap=True: the merge takes the insert sizes the overlap search finds")
+        _check_int("merge_quality_cap", merge_quality_cap, 0, 255)
     plans, stats = [], {}
     codes1, codes2 = (_adapter_codes(a) if a is not None else None for a in (adapters1, adapters2))
     for name, cols, codes in (("read1", cols1, codes1), ("read2", cols2, codes2)):
@@ -438,7 +514,15 @@ def filter_pairs(handle: _lib.Handle, cols1: RecordColumns, cols2: RecordColumns
                                                      rules.get("min_length", 1))
             side = dict(side, adapter=a_stats)
         plans.append((begin, end, keep)); stats[name] = side
-    if overlap:
+    merged = None
+    if merge:
+        b1, e1, b2, e2, keep, p_stats, insert = pair_plan(handle, cols1, cols2, plans[0], plans[1], pair_min_overlap, pair_max_mismatches,
+                                                          pair_max_error_permille, rules.get("min_length", 1), return_insert=True)
+        stats["pair"] = p_stats
+        merged, flag, stats["merge"] = merge_pairs(handle, cols1, cols2, b1, e1, b2, e2, keep, insert, pair_min_overlap, pair_max_mismatches,
+                                                   pair_max_error_permille, merge_quality_cap, titles=titles)
+        keep = keep & (flag ^ 1)                             # both hold 0 / 1
+    elif overlap:
         b1, e1, b2, e2, keep, p_stats = pair_plan(handle, cols1, cols2, plans[0], plans[1], pair_min_overlap, pair_max_mismatches,
                                                   pair_max_error_permille, rules.get("min_length", 1))
         stats["pair"] = p_stats
@@ -451,4 +535,4 @@ def filter_pairs(handle: _lib.Handle, cols1: RecordColumns, cols2: RecordColumns
             stats[name] = dict(stats[name], profile_before=before, profile_after=profile_columns(handle, cols, b, e, keep, n_cycles=before.n_cycles))
     out1 = select_columns(handle, cols1, b1, e1, keep, titles=titles)
     out2 = select_columns(handle, cols2, b2, e2, keep, titles=titles)
-    return out1, out2, stats
+    return (out1, out2, merged, stats) if merge else (out1, out2, stats)

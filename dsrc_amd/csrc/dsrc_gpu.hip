@@ -49,6 +49,7 @@
 #include "k_columns_sel.h"
 #include "k_columns_adapt.h"
 #include "k_columns_pair.h"
+#include "k_columns_merge.h"
 #include "k_columns_profile.h"
 
 namespace
@@ -2458,6 +2459,88 @@ int dsrcgpu_columns_pair_plan(dsrcgpu_handle* h, const dsrcgpu_columns_in* in1, 
 			return fail(h, rc, "pair plan, read %u: %s", side + 1, why.c_str());
 		}
 	for (u32 k = 0; k < PAIR_N_STATS; ++k) stats[k] = res[k + 2];
+	return DSRCGPU_OK;
+}
+
+// the merge (k_columns_merge.h): the check pass per side as in the pair plan, the judge, then the select's three-launch placement over
+// the judge's verdicts; the error words, the statistics and the totals come home in one copy, in front of the first kernel that writes
+// the caller's arrays
+int dsrcgpu_columns_merge_device(dsrcgpu_handle* h, const dsrcgpu_columns_in* in1, const dsrcgpu_columns_in* in2, const dsrcgpu_merge_rules* rules,
+								 const uint64_t* d_begin1, const uint64_t* d_end1, const uint64_t* d_begin2, const uint64_t* d_end2, const uint8_t* d_keep,
+								 const uint64_t* d_insert, const dsrcgpu_columns* out, uint8_t* d_merged, uint64_t* d_source, uint64_t totals[3],
+								 uint64_t stats[12])
+{
+	if (!h) return DSRCGPU_E_ARG;
+	if (!rules || !totals || !stats || !out) return fail(h, DSRCGPU_E_ARG, "null argument");
+	totals[0] = totals[1] = totals[2] = 0;
+	for (u32 k = 0; k < MERGE_N_STATS; ++k) stats[k] = 0;
+	if (!out->d_titles && out->titles_cap) return fail(h, DSRCGPU_E_ARG, "columns: titles_cap without d_titles");
+	const bool titles = out->d_titles != nullptr;
+	ColIn c1, c2;
+	{ const int rc = sel_in_args(h, in1, titles, c1); if (rc) return rc; }
+	{ const int rc = sel_in_args(h, in2, false, c2); if (rc) return rc; }
+	if (c1.n_recs != c2.n_recs) return fail(h, DSRCGPU_E_ARG, "merge: %llu records of read 1, %llu of read 2", (unsigned long long)c1.n_recs, (unsigned long long)c2.n_recs);
+	if (rules->min_overlap < 1) return fail(h, DSRCGPU_E_ARG, "merge rules: min_overlap of 0");
+	if (rules->max_error_permille > 1000) return fail(h, DSRCGPU_E_ARG, "merge rules: max_error_permille above 1000");
+	if (rules->quality_cap > 255) return fail(h, DSRCGPU_E_ARG, "merge rules: quality_cap above 255");
+	if (rules->reserved[0] | rules->reserved[1] | rules->reserved[2] | rules->reserved[3]) return fail(h, DSRCGPU_E_ARG, "merge rules: reserved fields must be 0");
+	if (!d_begin1 != !d_end1) return fail(h, DSRCGPU_E_ARG, "columns: d_begin1 and d_end1 go together");
+	if (!d_begin2 != !d_end2) return fail(h, DSRCGPU_E_ARG, "columns: d_begin2 and d_end2 go together");
+	if (!d_insert || !d_merged) return fail(h, DSRCGPU_E_ARG, "null argument");
+	HIPCHK(hipSetDevice(h->device));
+	hipStream_t s = h->stream;
+	const auto nothing_merged = [&]() -> int {
+		if (c1.n_recs) HIPCHK(hipMemsetAsync(d_merged, 0, (size_t)c1.n_recs, s));
+		if (out->d_seq_offs) HIPCHK(hipMemsetAsync(out->d_seq_offs, 0, sizeof(u64), s));
+		if (titles && out->d_title_offs) HIPCHK(hipMemsetAsync(out->d_title_offs, 0, sizeof(u64), s));
+		HIPCHK(hipStreamSynchronize(s));
+		return DSRCGPU_OK;
+	};
+	if (c1.n_recs == 0) return nothing_merged();
+	const u64 n_tiles = (c1.n_recs + WG - 1) / WG;
+	const u32 n_res = 2 + MERGE_N_STATS + 3;             // an error word per side, the twelve statistics, the three totals
+	{ const int rc = ensure_arena(h, (size_t)(3 * n_tiles + 2 * c1.n_recs + n_res) * 8 + 4096); if (rc) return rc; }
+	const size_t o_res = h->arena.alloc(n_res * 8), o_tiles = h->arena.alloc((size_t)n_tiles * 24), o_len = h->arena.alloc((size_t)c1.n_recs * 8),
+	             o_pos = h->arena.alloc((size_t)c1.n_recs * 8);
+	if (h->arena.failed) return fail(h, DSRCGPU_E_NOMEM, "arena exhausted (columns merge)");
+	u64* d_res = AP<u64>(h, o_res); u64* d_tiles = AP<u64>(h, o_tiles); u64* d_len = AP<u64>(h, o_len); u64* d_pos = AP<u64>(h, o_pos);
+	HIPCHK(hipMemsetAsync(d_res, 0xFF, 2 * 8, s));
+	HIPCHK(hipMemsetAsync(d_res + 2, 0, (n_res - 2) * 8, s));
+	HIPCHK(hipMemsetAsync(d_len, 0xFF, (size_t)c1.n_recs * 8, s));      // MERGE_NOT: a pair the judge does not reach is not merged
+	const MergeWhat w{AdaptPlanIn{d_begin1, d_end1, nullptr}, AdaptPlanIn{d_begin2, d_end2, nullptr}, d_keep, d_insert};
+	const MergeRules R{rules->min_overlap, rules->max_mismatches, rules->max_error_permille, rules->quality_cap};
+	const u64 wpg = WG / 64;
+	const dim3 g_check((u32)std::max<u64>(1, std::min<u64>(1024, (c1.n_recs + WG - 1) / WG)));
+	const dim3 g_waves((u32)std::max<u64>(1, std::min<u64>(4096, (c1.n_recs + wpg - 1) / wpg)));
+	const u32 g_tiles = (u32)std::min<u64>(4096, n_tiles);
+	hipLaunchKernelGGL(k_adapt_check, g_check, dim3(WG), 0, s, c1, w.w1, d_res); KCHK();
+	hipLaunchKernelGGL(k_adapt_check, g_check, dim3(WG), 0, s, c2, w.w2, d_res + 1); KCHK();
+	hipLaunchKernelGGL(k_merge_judge, g_waves, dim3(WG), 0, s, c1, c2, w, R, d_len, d_res + 2, d_res); KCHK();
+	hipLaunchKernelGGL(k_merge_tiles, dim3(g_tiles), dim3(WG), 0, s, c1, d_len, titles ? 1u : 0u, n_tiles, d_tiles, d_res); KCHK();
+	hipLaunchKernelGGL(k_sel_scan_tiles, dim3(1), dim3(WG), 0, s, n_tiles, d_tiles, d_res + 2 + MERGE_N_STATS); KCHK();
+	u64 res[2 + MERGE_N_STATS + 3];
+	HIPCHK(hipMemcpyAsync(res, d_res, sizeof(res), hipMemcpyDeviceToHost, s));
+	HIPCHK(hipStreamSynchronize(s));
+	for (u32 side = 0; side < 2; ++side)
+		if (res[side] != COLE_NONE)
+		{
+			const int rc = sel_input_error(h, res[side]);
+			const std::string why = dsrcgpu_last_error(h);
+			return fail(h, rc, "merge, read %u: %s", side + 1, why.c_str());
+		}
+	for (u32 k = 0; k < MERGE_N_STATS; ++k) stats[k] = res[2 + k];
+	const u64* const tot = res + 2 + MERGE_N_STATS;
+	totals[0] = tot[0]; totals[1] = tot[1]; totals[2] = tot[2];
+	if (out->records_cap < tot[0] || out->bases_cap < tot[1] || out->quals_cap < tot[1] || (titles && out->titles_cap < tot[2]))
+		return fail(h, DSRCGPU_E_CAPACITY, "merge: %llu records, %llu bases, %llu title bytes come out; the caller's arrays hold %llu, %llu / %llu, %llu",
+		            (unsigned long long)tot[0], (unsigned long long)tot[1], (unsigned long long)tot[2], (unsigned long long)out->records_cap,
+		            (unsigned long long)out->bases_cap, (unsigned long long)out->quals_cap, (unsigned long long)out->titles_cap);
+	if (tot[0] == 0) return nothing_merged();
+	if (!out->d_seq_offs || (titles && !out->d_title_offs) || !out->d_bases || !out->d_quals) return fail(h, DSRCGPU_E_ARG, "columns: null output array");
+	const SelOut o{out->d_bases, out->d_quals, out->d_titles, out->d_seq_offs, out->d_title_offs, d_source, tot[0], tot[1], tot[2]};
+	hipLaunchKernelGGL(k_merge_apply, dim3(g_tiles), dim3(WG), 0, s, c1, d_len, titles ? 1u : 0u, n_tiles, d_tiles, o, d_merged, d_pos); KCHK();
+	hipLaunchKernelGGL(k_merge_write, g_waves, dim3(WG), 0, s, c1, c2, w, R, d_len, d_pos, o, titles ? 1u : 0u); KCHK();
+	HIPCHK(hipStreamSynchronize(s));
 	return DSRCGPU_OK;
 }
 

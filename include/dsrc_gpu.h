@@ -324,8 +324,8 @@ int dsrcgpu_columns_adapter_plan(dsrcgpu_handle* h, const dsrcgpu_columns_in* in
  * counted as such, its ranges pass through and the keep rule still applies to it.  d_keep[r] = 1 iff both mates came in kept and n1' >=
  * min_length and n2' >= min_length.  A pair that came in with a mate dropped passes its ranges through with d_keep[r] = 0; if exactly one
  * mate had been kept it counts in "dropped for the mate", if neither, in nothing.
- * Not done here: indels, base correction in the overlap, merging the mates into one read, a check that the mates' titles agree,
- * interleaved input, the "best" overlap instead of the first accepted one.
+ * Not done here: indels, a check that the mates' titles agree, interleaved input, the "best" overlap instead of the first accepted one.
+ * (Base correction in the overlap and merging the mates into one read: dsrcgpu_columns_merge_device, below, which takes d_insert.)
  * stats (host): [0] pairs kept, [1] / [2] bases kept of read 1 / read 2, [3] / [4] bases this call cut off read 1 / read 2 of kept pairs,
  * [5] pairs in which an overlap was found, [6] of those, pairs in which either range became shorter, [7] pairs dropped for the mate,
  * [8] pairs dropped for length (both mates came in kept), [9] pairs not searched for a range above DSRCGPU_PAIR_MAX_BASES, [10] the sum
@@ -357,6 +357,86 @@ int dsrcgpu_columns_pair_plan(dsrcgpu_handle* h, const dsrcgpu_columns_in* in1, 
 		uint8_t* d_keep                                                                     /* device, n_records: the pair's flag */,
 		uint64_t* d_insert                                                                  /* device, n_records, may be NULL */,
 		uint64_t stats[11]);
+
+/* dsrcgpu_columns_merge_device: what the insert size of the pair plan is for -- the two mates of a short insert become ONE read with
+ * a consensus where they overlap (fastp --merge, PEAR, FLASH, BBMerge).  The first columnar call that writes new bases and qualities
+ * instead of copying ranges.  It takes the pair plan's outputs -- the ranges, the pair's keep flag and d_insert -- and writes the merged
+ * reads into `out` as dsrcgpu_columns_select_device writes its records: in pair order, offsets from 0.  d_merged[r] = 1 iff pair r is in
+ * `out`; the caller selects the unmerged mates with keep & !merged.
+ * Conventions as dsrcgpu_columns_select_device and dsrcgpu_columns_pair_plan: the handle's own lane and stream, scratch (a few words per
+ * pair) from the arena, synchronised before it returns, codec state left alone, a colour-space handle: DSRCGPU_E_ARG.  d_bases, d_quals
+ * and d_seq_offs of both sides are read; titles are taken from `in1` only, and only when out->d_titles is wanted: in2's titles may be NULL.
+ * The ranges: d_begin<s> / d_end<s> (both NULL = whole reads; one without the other: DSRCGPU_E_ARG; the sides are independent); d_keep
+ * (NULL = every pair; any non-zero byte keeps); d_insert is required and is caller data like any other: nothing about it is trusted.
+ * For pair r, side s in {1, 2}: [b_s, e_s) its range in its own d_bases, S_s its record start, f_s = b_s - S_s, n_s = e_s - b_s,
+ * I = d_insert[r].  In insert coordinates read 1's range lies at [a1, z1) = [f1, f1 + n1), the reverse complement of read 2's range at
+ * [a2, z2) = [I - f2 - n2, I - f2).  At insert position p
+ *   read 1 gives c1 = bases1[b1 + p - a1],               q1 = quals1[b1 + p - a1]                (a1 <= p < z1)
+ *   read 2 gives c2 = COMP[bases2[e2 - 1 - (p - a2)]],   q2 = quals2[e2 - 1 - (p - a2)]          (a2 <= p < z2)
+ * COMP over the code alphabet "ACGTNRWSKMDVHBYXU.-" (A<->T, C<->G, R<->Y, K<->M, D<->H, V<->B; N W S X . - themselves; U -> A), a code
+ * above 18 is itself:
+ *   code   0  1  2  3  4  5  6  7  8  9 10 11 12 13 14 15 16 17 18
+ *          A  C  G  T  N  R  W  S  K  M  D  V  H  B  Y  X  U  .  -
+ *   COMP   3  2  1  0  4 14  6  7  9  8 12 13 10 11  5 15  0 17 18
+ * c2 is the code BEHIND the table everywhere below: a U of read 2 is an A, code 0, and counts as one of A C G T.
+ *   if d_keep[r] == 0:                                         not merged, stats[7]
+ *   else if I == 2^64 - 1:                                     not merged, stats[8]
+ *   else if I >= 2^40 or n1 == 0 or n2 == 0 or I < f2 + n2 or f1 + n1 > I:
+ *                                                              not merged, stats[9]  (I < f2 + n2: read 2 runs past the start of the
+ *                                                              insert, the plan was not narrowed; f1 + n1 > I: read 1 past its end)
+ *   else:
+ *     V = min(z1, z2) - max(a1, a2)                            (signed: a gap between the ranges is negative)
+ *     if V < min_overlap:                                      not merged, stats[10]
+ *     else:
+ *       mm = the number of p in [max(a1, a2), min(z1, z2)) with c1 != c2 or c1 >= 4 or c2 >= 4
+ *       if mm > max_mismatches or mm * 1000 > V * max_error_permille:
+ *                                                              not merged, stats[11]
+ *       else merged: for p = min(a1, a2) .. max(z1, z2) - 1 the output read gets
+ *         p in one range only:                 that read's (c, q)
+ *         c1 < 4, c2 < 4, c1 == c2:            (c1, min(q1 + q2, max(quality_cap, q1, q2)))     stats[3]
+ *         c1 < 4, c2 < 4, c1 != c2:            q1 >= q2 ? (c1, q1 - q2) : (c2, q2 - q1)         stats[4]  (read 1 wins a tie, quality 0)
+ *         exactly one of c1, c2 < 4:           that one with its own quality                    stats[5]
+ *         neither < 4:                         (c1, min(q1, q2))                                stats[6]
+ *       stats[0] += 1; stats[1] += max(z1, z2) - min(a1, a2); stats[2] += V
+ * The merged record's title is read 1's, whole.  d_source (may be NULL) gets the pair index of each output record.
+ * stats (host): [0] pairs merged, [1] bases written, [2] the sum of V over merged pairs, [3] .. [6] the overlap positions of merged pairs
+ * by case as above, [7] .. [11] pairs not merged by reason as above.  Sums of integers: the result does not depend on the order in which
+ * the device takes the pairs.  [3] + [4] + [5] + [6] == [2] and [0] + [7] + .. + [11] == n_records.
+ * totals (host): records, bases, title bytes of `out`.  Capacities exactly as in dsrcgpu_columns_select_device: any too small:
+ * DSRCGPU_E_CAPACITY, totals = what is needed (stats are filled as well), none of the caller's arrays written, d_merged and d_source
+ * included (the totals come home before the first writing kernel is launched); a call with capacities of 0 sizes the arrays.
+ * out->d_titles == NULL with titles_cap 0: titles are not wanted, totals[2] is 0.
+ * DSRCGPU_E_ARG, nothing written: in1->n_records != in2->n_records; min_overlap 0; max_error_permille above 1000; quality_cap above 255;
+ * a non-zero reserved field; a half-given range pair; d_insert, d_merged, rules, totals, stats or out NULL; a NULL d_quals (or d_bases)
+ * with bases_len > 0.
+ * DSRCGPU_E_INPUT (outputs untouched), for kept and dropped pairs alike: the conditions of dsrcgpu_columns_pair_plan on either side;
+ * dsrcgpu_last_error names the side (read 1 is reported first), the lowest record of that side and the reason.  With titles wanted,
+ * in1's title offsets out of order or above titles_len as well, as in dsrcgpu_columns_select_device.
+ * Nothing merged, or n_records == 0: DSRCGPU_OK, totals 0, offs[0] = 0, d_merged all 0.
+ * The arrays of `in1` / `in2`, the ranges, d_keep and d_insert on one side and the arrays of `out`, d_merged and d_source on the other
+ * must not overlap; this is not checked.  No input makes a kernel read or write outside the caller's arrays: a pair's offsets, ranges
+ * and geometry are tested before a byte of it is read.
+ * Not done here: indels, a new search (d_insert is taken as given), a title suffix such as fastp's merged_x_y, a check that the mates'
+ * titles agree, writing the unmerged mates (two selects with keep & !merged), interleaved input. */
+typedef struct dsrcgpu_merge_rules
+{
+	uint32_t min_overlap;           /* >= 1 */
+	uint32_t max_mismatches;
+	uint32_t max_error_permille;    /* 0 .. 1000 */
+	uint32_t quality_cap;           /* 0 .. 255: ceiling of a summed quality */
+	uint32_t reserved[4];           /* must be 0 */
+} dsrcgpu_merge_rules;
+
+int dsrcgpu_columns_merge_device(dsrcgpu_handle* h, const dsrcgpu_columns_in* in1, const dsrcgpu_columns_in* in2,
+		const dsrcgpu_merge_rules* rules,
+		const uint64_t* d_begin1, const uint64_t* d_end1   /* device, both NULL = whole reads */,
+		const uint64_t* d_begin2, const uint64_t* d_end2,
+		const uint8_t* d_keep                              /* device, NULL = every pair */,
+		const uint64_t* d_insert                           /* device, required: as dsrcgpu_columns_pair_plan wrote it */,
+		const dsrcgpu_columns* out                         /* merged reads, capacities as in dsrcgpu_columns_select_device */,
+		uint8_t* d_merged                                  /* device, n_records: 1 = this pair is in `out`; required */,
+		uint64_t* d_source                                 /* device, may be NULL: pair index of each output record */,
+		uint64_t totals[3], uint64_t stats[12]);
 
 /* dsrcgpu_columns_profile: the per-cycle quality report of the records of `in` under a plan -- what one reads to choose quality_3,
  * min_length and the adapters, and to see what a filter did: the profile with no plan is "before", the profile of the same columns
