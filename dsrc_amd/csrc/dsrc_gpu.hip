@@ -1025,8 +1025,8 @@ int run_batch(dsrcgpu_handle* h, BatchIO io)
 			}
 			stage_mark(1);
 		}
-		// the serial coder runs on a stream of its own: its launch must not queue behind this instance's next kernels, nor they behind it (see dsrcgpu_create; the
-		// other instances' data-parallel kernels run beside it)
+		// the serial coder runs on a stream of its own, on a hardware queue no front end shares (dsrcgpu_create): the other instances'
+		// data-parallel kernels run beside it
 		HIPCHK(hipEventRecord(h->ev[4], s));
 		HIPCHK(hipStreamWaitEvent(h->rc_stream, h->ev[4], 0));
 		HIPCHK(hipEventRecord(h->ev[2], h->rc_stream));
@@ -1037,7 +1037,10 @@ int run_batch(dsrcgpu_handle* h, BatchIO io)
 		else hipLaunchKernelGGL(k_rcs<16>, dim3((NJ + 15) / 16), dim3(64 * RCS_WG_WAVES), 0, h->rc_stream, d_chains, NJ, AP<RcPack>(h, 0), wpool, d_state, (const u32*)d_bk, d_redo);
 		KCHK();
 		HIPCHK(hipEventRecord(h->ev[3], h->rc_stream));
-		HIPCHK(hipStreamWaitEvent(s, h->ev[3], 0));
+		// the front-end stream is told on the HOST that the coder has finished: a device-side wait parked in its hardware queue holds
+		// up, for the coder's 79 ms, whatever else shares that in-order queue (other instances' front ends, the embedder's streams);
+		// nothing of this instance can run meanwhile, and the host synchronises a few lines down anyway.  One launch latency.
+		HIPCHK(hipEventSynchronize(h->ev[3]));
 		h->rc_launches = 1;
 	}
 
@@ -1497,7 +1500,8 @@ int run_decode(dsrcgpu_handle* h, DecodeIO io)
 				if (sizes_present & 128u) { hipLaunchKernelGGL(k_dec_qrc<128>, dim3(r.count), dim3(64), 0, s, io.d_in, d_desc, d_state, tp, rp, d_out, h->dec_tables, prm); KCHK(); }
 			}
 		}
-		if (par) HIPCHK(hipStreamWaitEvent(s, h->ev[3], 0));
+		// (on the host, as in run_batch: no wait parked in the pooled queue; the quality rounds above are already enqueued and run meanwhile)
+		if (par) HIPCHK(hipEventSynchronize(h->ev[3]));
 		hipLaunchKernelGGL(k_dec_dhead, dim3((B + 63) / 64), dim3(64), 0, s, io.d_in, d_desc, d_state, prm, par ? (const DecHint*)AP<DecHint>(h, o_hints) : (const DecHint*)nullptr); KCHK();
 		bool any_plain = !d_rc;
 		if (par) { for (u32 b = 0; b < B; ++b) if (io.hints[b].d_scheme == 255) { any_plain = true; ++dbg_plain; } }
@@ -1736,12 +1740,20 @@ int dsrcgpu_create(const dsrcgpu_settings* settings, const dsrcgpu_dataset* data
 		// non-blocking: a host framework's work on the legacy default stream (torch, RCCL bookkeeping) must not
 		// serialise with the scheduler's streams.  (CUs reserved for k_rc through a CU mask were measured in rounds 2 and 4: no gain.)
 		HIPCHK(hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking));
-		// k_rc has a stream of its own, of the SAME priority as the front end's (round 5).  Rounds 1-4 gave it the highest: its few waves
-		// were not to queue behind other instances' data-parallel kernels.  Since the coder wave has its SIMD to itself and eight loader
-		// waves feed it, k_rc takes its 118 ms whatever runs beside it -- and the priority only held the front ends back: 4 x 450 blocks
-		// 52.3 - 54.8 GB/s with the high-priority stream, 55.1 - 56.7 without (three runs each, profiles/r05_rcprio.txt; the same
-		// through a CU-mask stream over all CUs, and confining k_rc to 16 / 32 / 64 CUs of an instance's own changed nothing beyond that).
-		HIPCHK(hipStreamCreateWithFlags(&h->rc_stream, hipStreamNonBlocking));
+		// The coder has a stream of its own, of the LOWEST priority (round 16) -- not for the priority: the HIP runtime keeps one pool of
+		// at most GPU_MAX_HW_QUEUES hardware queues PER PRIORITY and hands a pool's queues round to its streams once it is full, so a
+		// stream of another priority is the non-blocking way to a queue that no front-end stream, no null stream and no stream of the
+		// embedder's (all of normal priority) can land on.  With both streams in the normal pool and the runtime's default of 4 queues,
+		// four instances put a front end behind another instance's 79 ms k_rcs: 39.8 - 50.1 GB/s against 68.7 - 69.7 with 24 queues.
+		// Measured at 4 queues, 4 x 450 blocks, with run_batch waiting for the coder on the host (there; needed as well: alone, the
+		// queue of its own gives 47.9 - 48.0): lowest priority 63.3 - 64.0, highest 63.1 - 63.2, a CU-mask stream over all CUs (a queue
+		// outside the pools, but blocking towards the legacy default stream) 63.1 - 64.1, both streams normal 53.0 - 55.6 GB/s; k_rcs
+		// takes its 79 ms (0.8 more under the low priority) and starts within a millisecond of its event under all of them.  Where every
+		// stream has a queue anyway (24): highest 63.5 - 65.7, lowest 66.9 - 70.2, normal or CU mask 70.1 - 70.6 (NOTES/round_16.md, profiles/r16_*).
+		// More than GPU_MAX_HW_QUEUES handles: their coder streams share the low-priority queues among themselves, never with a front end.
+		int prio_least = 0, prio_greatest = 0;
+		HIPCHK(hipDeviceGetStreamPriorityRange(&prio_least, &prio_greatest));
+		HIPCHK(hipStreamCreateWithPriority(&h->rc_stream, hipStreamNonBlocking, prio_least));
 	}
 	for (int i = 0; i < 5; ++i) HIPCHK(hipEventCreate(&h->ev[i]));
 	h->arena_fixed = arena_bytes;
@@ -2965,12 +2977,15 @@ int dsrcgpu_device_memory(int device, uint64_t* free_bytes, uint64_t* total_byte
 	return DSRCGPU_OK;
 }
 
-// Every scheduler instance drives two HIP streams, and the HIP runtime multiplexes streams onto 4 hardware queues unless
-// GPU_MAX_HW_QUEUES says otherwise: unrelated instances then wait behind each other's range coder (7.7 instead of 12.9 GB/s,
-// DESIGN section 3).  The runtime reads the variable when it starts, i.e. at the process's first HIP call.  The library does NOT
-// touch the environment on its own when it is loaded (an embedding application's queue configuration is its own business):
-// dsrcgpu_prepare is the opt-in -- a host that calls it before its first HIP call (dsrc-amd, pydsrc, bench.py do) gets 24 queues
-// unless the process has already chosen a value; everybody else exports the variable themselves.
+// Every scheduler instance drives two HIP streams, and the HIP runtime multiplexes the streams of one priority onto 4 hardware
+// queues unless GPU_MAX_HW_QUEUES says otherwise.  NEEDED since round 16: nothing -- the coder's stream has a queue outside the pool the
+// front ends share (dsrcgpu_create) and no front-end stream holds a device-side wait for the coder (run_batch, run_decode), so
+// instances overlap with the default of 4 (4 x 450 blocks: 68.5 - 68.8 GB/s with 4 queues, 68.1 - 69.6 with 24), also in a process that
+// started HIP before it loaded the library.  HELPFUL still: with more handles (or lanes) than pooled queues several FRONT ENDS share an
+// in-order queue and their kernels take turns.  The runtime reads the variable when it starts, i.e. at the process's first HIP call.
+// The library does NOT touch the environment on its own when it is loaded (an embedding application's queue configuration is its
+// own business): dsrcgpu_prepare is the opt-in -- a host that calls it before its first HIP call (dsrc-amd, pydsrc do) gets 24 queues
+// unless the process has already chosen a value.
 
 int dsrcgpu_prepare(int device)
 {

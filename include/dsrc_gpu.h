@@ -587,9 +587,12 @@ int dsrcgpu_release_memory(dsrcgpu_handle* h);
 int dsrcgpu_reserve_memory(dsrcgpu_handle* h, uint64_t arena_bytes, uint64_t table_bytes);
 
 /* Optional: brings up the HIP runtime and the device context (the first HIP call of a process costs 0.3-1 s); call it on a
- * side thread while the host opens its files.  It is also the opt-in for the queue setting several handles per device need:
+ * side thread while the host opens its files.  It is also the opt-in for a queue setting that helps several handles per device:
  * when the process has not set GPU_MAX_HW_QUEUES, the first call sets it to 24 -- effective only if this is the process's first
- * HIP call (the runtime reads the variable when it starts).  The library never touches the environment otherwise. */
+ * HIP call (the runtime reads the variable when it starts).  The library never touches the environment otherwise.  No handle
+ * NEEDS the setting: every handle's range coder runs on a hardware queue that no front-end stream shares, whatever the variable
+ * says, so handles overlap with the runtime's default of 4 queues as well (and in a process that started HIP earlier); with more
+ * handles or lanes than queues only their data-parallel front ends take turns on a queue. */
 int dsrcgpu_prepare(int device);
 
 /* Page-locked host memory for chunk / block buffers: host<->device copies from it run at PCIe speed and
