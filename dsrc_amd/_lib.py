@@ -27,7 +27,7 @@ EXPORTS = [
     "dsrcgpu_synth_fastq", "dsrcgpu_reserve_memory", "dsrcgpu_set_lanes", "dsrcgpu_submit_pinned",
     "dsrcgpu_decompress_batch_columns_device", "dsrcgpu_compress_columns_device", "dsrcgpu_columns_cut",
     "dsrcgpu_columns_trim_plan", "dsrcgpu_columns_select_device", "dsrcgpu_columns_adapter_plan", "dsrcgpu_columns_pair_plan",
-    "dsrcgpu_columns_profile", "dsrcgpu_columns_merge_device",
+    "dsrcgpu_columns_profile", "dsrcgpu_columns_merge_device", "dsrcgpu_columns_dedup_plan",
 ]
 
 # error codes of include/dsrc_gpu.h that callers tell apart (DsrcGpuError.code)
@@ -131,6 +131,25 @@ class MergeRules(C.Structure):
 
 MERGE_STATS = ("pairs_merged", "bases_written", "overlap_sum", "overlap_agree", "overlap_corrected", "overlap_one_sided", "overlap_neither",
                "not_kept", "no_insert", "bad_geometry", "short_overlap", "over_budget")
+
+
+class DedupRules(C.Structure):
+    """dsrcgpu_dedup_rules: DedupRules(key_bases, prefer, hash_bits): key_bases 0 = the whole range; prefer 0 = the first record of a
+    class survives, 1 = the one with the highest quality sum; hash_bits is a diagnostic (0 or 64: the full hash) on which no result
+    depends.  The library is the one that refuses figures out of range."""
+    _fields_ = [("key_bases", C.c_uint32), ("prefer", C.c_uint32), ("hash_bits", C.c_uint32), ("reserved", C.c_uint32 * 5)]
+
+    def __init__(self, key_bases=0, prefer=0, hash_bits=0, reserved=(0, 0, 0, 0, 0)):
+        super().__init__()
+        self.key_bases, self.prefer, self.hash_bits = key_bases, prefer, hash_bits
+        self.reserved = (C.c_uint32 * 5)(*reserved)
+
+
+DEDUP_PREFER = {"first": 0, "quality": 1}
+DEDUP_STATS = ("records_considered", "records_kept", "records_dropped", "classes_multiple", "largest_class", "came_in_dropped", "empty_keys",
+               "representative_not_first") + tuple("level_" + b for b in ("1", "2", "3", "4", "5", "6", "7", "8", "9", "10_49", "50_99", "100_499", "500_999",
+                                                                           "1000_4999", "5000_9999", "10000_up"))
+NO_DUP_OF = 0xFFFFFFFFFFFFFFFF   # d_dup_of of a record that came in dropped
 
 
 class ProfileRules(C.Structure):
@@ -501,6 +520,21 @@ class Handle:
                                                    C.c_void_p(k1), C.c_void_p(b2), C.c_void_p(e2), C.c_void_p(k2), C.c_void_p(d_begin1),
                                                    C.c_void_p(d_end1), C.c_void_p(d_begin2), C.c_void_p(d_end2), C.c_void_p(d_keep),
                                                    C.c_void_p(d_insert), stats))
+        return list(stats)
+
+    def columns_dedup_plan(self, cols_in1: ColumnsIn, cols_in2, rules: DedupRules, ranges1, ranges2, d_keep_in, d_keep: int, d_dup_of=None,
+                           d_copies=None):
+        """dsrcgpu_columns_dedup_plan: exact duplicates among the records of cols_in1 (cols_in2 None) or among the pairs cols_in1 /
+        cols_in2.  ranges<s> is the pair (d_begin, d_end) of side s (device addresses or None: whole reads), d_keep_in the incoming
+        flag (or None: every record); d_keep (uint8) gets 1 for the one record of every class that survives -- it may be the very
+        array d_keep_in --, d_dup_of (uint64, or None) the surviving record's index (NO_DUP_OF for a record that came in dropped),
+        d_copies (uint64, or None) the class size at the survivor and 0 elsewhere, all device memory of n_records entries.  Returns
+        the 24 statistics (DEDUP_STATS names them)."""
+        stats = (C.c_uint64 * 24)()
+        (b1, e1), (b2, e2) = ranges1, ranges2
+        self._chk(self.L.dsrcgpu_columns_dedup_plan(self.h, C.byref(cols_in1), C.byref(cols_in2) if cols_in2 is not None else None, C.byref(rules),
+                                                    C.c_void_p(b1), C.c_void_p(e1), C.c_void_p(b2), C.c_void_p(e2), C.c_void_p(d_keep_in),
+                                                    C.c_void_p(d_keep), C.c_void_p(d_dup_of), C.c_void_p(d_copies), stats))
         return list(stats)
 
     def columns_merge_device(self, cols_in1: ColumnsIn, cols_in2: ColumnsIn, rules: MergeRules, ranges1, ranges2, d_keep, d_insert, out: Columns,

@@ -1,8 +1,8 @@
 """Records as torch tensors: decode_columns (dsrcgpu_decompress_batch_columns_device), the way back, encode_columns
 (dsrcgpu_compress_columns_device), and what runs between the two: trim_plan (dsrcgpu_columns_trim_plan), adapter_plan
-(dsrcgpu_columns_adapter_plan), pair_plan (dsrcgpu_columns_pair_plan), merge_pairs (dsrcgpu_columns_merge_device), select_columns
-(dsrcgpu_columns_select_device), filter_columns and, for paired-end data, filter_pairs, and the report on either side of them,
-profile_columns (dsrcgpu_columns_profile), include/dsrc_gpu.h.
+(dsrcgpu_columns_adapter_plan), pair_plan (dsrcgpu_columns_pair_plan), dedup_plan (dsrcgpu_columns_dedup_plan), merge_pairs
+(dsrcgpu_columns_merge_device), select_columns (dsrcgpu_columns_select_device), filter_columns and, for paired-end data,
+filter_pairs, and the report on either side of them, profile_columns (dsrcgpu_columns_profile), include/dsrc_gpu.h.
 
 The blocks are already in device memory; the arrays are allocated by torch on the same device and filled by the library's
 kernels -- no text, no host round trip of the payload.  With the emulator build of the library (tests/emu) device pointers
@@ -338,21 +338,30 @@ def profile_columns(handle: _lib.Handle, cols: RecordColumns, begin=None, end=No
 
 
 def filter_columns(handle: _lib.Handle, cols: RecordColumns, titles: bool = True, adapters=None, adapter_min_overlap: int = 3,
-                   adapter_max_error_permille: int = 100, profile: bool = False, **rules):
+                   adapter_max_error_permille: int = 100, profile: bool = False, dedup: bool = False, dedup_key_bases: int = 0,
+                   dedup_prefer: str = "first", **rules):
     """trim_plan(**rules) and select_columns with its plan in sequence: -> (RecordColumns of the trimmed, kept records, stats).
     adapters (see adapter_plan): between the two, adapter_plan narrows the trim plan -- the quality trim first, the adapter second,
     the order of cutadapt and fastp -- with the same min_length; stats is then the trim plan's dict plus a key "adapter" that holds
     the adapter plan's dict, and the number of records that come out is stats["adapter"]["records_kept"].  max_n and
     min_mean_quality were judged on the range before the adapter cut.
     profile=True: stats gets "profile_before", the ColumnsProfile of `cols` as they came, and "profile_after", that of the records
-    that come out -- taken from the final plan on `cols`, with the same n_cycles."""
+    that come out -- taken from the final plan on `cols`, with the same n_cycles.
+    dedup=True: last among the plans, dedup_plan(key_bases=dedup_key_bases, prefer=dedup_prefer) on the final ranges and keep leaves one
+    record of every set of exact duplicates; stats gets "dedup", its dict, the number of records that come out is
+    stats["dedup"]["records_kept"], and "profile_after" reflects it."""
     if adapters is not None:
         codes = _adapter_codes(adapters)
+    if dedup:
+        _check_dedup_args(dedup_key_bases, dedup_prefer)
     begin, end, keep, stats = trim_plan(handle, cols, **rules)
     if adapters is not None:
         begin, end, keep, a_stats = adapter_plan(handle, cols, codes, begin, end, keep, adapter_min_overlap, adapter_max_error_permille,
                                                  rules.get("min_length", 1))
         stats = dict(stats, adapter=a_stats)
+    if dedup:
+        keep, d_stats = dedup_plan(handle, cols, begin=begin, end=end, keep=keep, key_bases=dedup_key_bases, prefer=dedup_prefer)
+        stats = dict(stats, dedup=d_stats)
     if profile:
         before = profile_columns(handle, cols)
         stats = dict(stats, profile_before=before, profile_after=profile_columns(handle, cols, begin, end, keep, n_cycles=before.n_cycles))
@@ -416,6 +425,62 @@ def pair_plan(handle: _lib.Handle, cols1: RecordColumns, cols2: RecordColumns, p
     del held1, held2
     got = (out[0], out[1], out[2], out[3], keep, dict(zip(_lib.PAIR_STATS, stats)))
     return got + (insert,) if return_insert else got          # (2^64 - 1 read as int64 is -1)
+
+
+def _check_dedup_args(key_bases, prefer):
+    _check_int("key_bases", key_bases, 0, 0xFFFFFFFF)
+    if not isinstance(prefer, str) or prefer not in _lib.DEDUP_PREFER:
+        raise ValueError("prefer must be one of %s" % ", ".join(repr(k) for k in _lib.DEDUP_PREFER))
+
+
+def dedup_plan(handle: _lib.Handle, cols: RecordColumns, cols2=None, begin=None, end=None, begin2=None, end2=None, keep=None, key_bases: int = 0,
+               prefer: str = "first", return_dup_of: bool = False, return_copies: bool = False):
+    """dsrcgpu_columns_dedup_plan on the records of `cols`, or -- with cols2, record r of which is the mate of record r of `cols` -- on
+    the pairs: of the considered records (keep non-zero, or keep None) whose keys are equal byte for byte exactly one survives ->
+    (keep, stats[, dup_of][, copies]) in fresh tensors.  The key of a record is its range begin / end (None: the whole read), or its
+    first key_bases bases (0: all of it), with its length; with cols2 the mate's range begin2 / end2 goes on behind it, and a pair is a
+    duplicate only if both mates are.  prefer="first": the lowest index of a class survives; "quality": the member with the highest sum
+    of qualities over the key positions, the lowest index on a tie.  keep (uint8) is 1 for the survivors; stats is a dict with the
+    keys of _lib.DEDUP_STATS (counts, and the duplication-level histogram in FastQC's bins); dup_of (int64) is the survivor's index
+    for every considered record, -1 for a record that came in dropped; copies (int64) is the class size at a survivor, 0 elsewhere.
+    No reverse complement, no mismatches, nothing across calls.  Arguments out of range, half-given ranges, ranges of side 2
+    without cols2, mis-sized tensors and column sets of different record counts or devices raise ValueError before the library is
+    called.  Nothing of the payload crosses to the host."""
+    _check_dedup_args(key_bases, prefer)
+    device = cols.bases.device
+    R = cols.n_records
+    if cols2 is not None:
+        if cols2.n_records != R:
+            raise ValueError("the mates come in equal numbers: %d records of read 1, %d of read 2" % (R, cols2.n_records))
+        if cols2.bases.device != device:
+            raise ValueError("both column sets live on one device")
+    elif begin2 is not None or end2 is not None:
+        raise ValueError("begin2 and end2 need cols2")
+    if (begin is None) != (end is None) or (begin2 is None) != (end2 is None):
+        raise ValueError("begin and end go together")
+    if R > 1 << 31:
+        raise ValueError("at most 2^31 records in one call")
+    i64s = [None if t is None else t.to(torch.int64).contiguous() for t in (begin, end, begin2, end2)]
+    if keep is not None:
+        keep = keep.to(torch.uint8).contiguous()
+    for t in i64s + [keep]:
+        if t is not None and (t.numel() != R or t.device != device):
+            raise ValueError("begin, end and keep have one entry per record, on the device of the columns")
+    cin1, held1 = _columns_in(cols, titles=False)
+    cin2, held2 = _columns_in(cols2, titles=False) if cols2 is not None else (None, None)
+    adr = lambda t: None if t is None or not t.numel() else t.data_ptr()
+    out_keep = torch.empty(R, dtype=torch.uint8, device=device)
+    dup_of = torch.empty(R, dtype=torch.int64, device=device) if return_dup_of else None
+    copies = torch.empty(R, dtype=torch.int64, device=device) if return_copies else None
+    rules = _lib.DedupRules(key_bases, _lib.DEDUP_PREFER[prefer])
+    _quiesce(device)
+    stats = handle.columns_dedup_plan(cin1, cin2, rules, (adr(i64s[0]), adr(i64s[1])), (adr(i64s[2]), adr(i64s[3])), adr(keep), adr(out_keep),
+                                      adr(dup_of), adr(copies))
+    del held1, held2
+    got = (out_keep, dict(zip(_lib.DEDUP_STATS, stats)))
+    if return_dup_of:
+        got += (dup_of,)                                     # (2^64 - 1 read as int64 is -1)
+    return got + (copies,) if return_copies else got
 
 
 def merge_pairs(handle: _lib.Handle, cols1: RecordColumns, cols2: RecordColumns, begin1=None, end1=None, begin2=None, end2=None, keep=None,
@@ -487,7 +552,7 @@ def merge_pairs(handle: _lib.Handle, cols1: RecordColumns, cols2: RecordColumns,
 def filter_pairs(handle: _lib.Handle, cols1: RecordColumns, cols2: RecordColumns, titles: bool = True, adapters1=None, adapters2=None,
                  overlap: bool = True, pair_min_overlap: int = 30, pair_max_mismatches: int = 5, pair_max_error_permille: int = 200,
                  adapter_min_overlap: int = 3, adapter_max_error_permille: int = 100, profile: bool = False, merge: bool = False,
-                 merge_quality_cap: int = 41, **rules):
+                 merge_quality_cap: int = 41, dedup: bool = False, dedup_key_bases: int = 0, dedup_prefer: str = "first", **rules):
     """filter_columns for paired-end data: per side trim_plan(**rules) and, if adapters<s> is given, adapter_plan; then pair_plan with
     the same min_length, which cuts read-through found from the overlap of the mates and decides per PAIR; then one select_columns per
     side with that side's ranges and the joint keep -> (out1, out2, stats), out1.n_records == out2.n_records always and record j of
@@ -499,7 +564,12 @@ def filter_pairs(handle: _lib.Handle, cols1: RecordColumns, cols2: RecordColumns
     min_overlap, max_mismatches and max_error_permille, and merge_quality_cap turns the kept pairs whose mates overlap into one read
     each; the two selects then take keep & ~merged -> (out1, out2, merged, stats): `merged` the RecordColumns of the merged reads,
     out1 / out2 the mates of the kept pairs that were not merged, stats["merge"] the dict of merge_pairs; merged.n_records +
-    out1.n_records is the pair plan's pairs_kept, and "profile_after" is that of out1 / out2."""
+    out1.n_records is the pair plan's pairs_kept, and "profile_after" is that of out1 / out2.
+    dedup=True: behind the pair plan (overlap=False: on keep1 & keep2) and in front of the merge, dedup_plan(key_bases=dedup_key_bases,
+    prefer=dedup_prefer) keyed on BOTH mates' final ranges leaves one pair of every set of exact duplicate pairs; stats["dedup"] is its
+    dict, the pairs that come out -- merged ones included -- number stats["dedup"]["records_kept"], and "profile_after" reflects it."""
+    if dedup:
+        _check_dedup_args(dedup_key_bases, dedup_prefer)
     _check_pair_args(cols1, cols2, pair_min_overlap, pair_max_mismatches, pair_max_error_permille, rules.get("min_length", 1))
     if merge:
         if not overlap:
@@ -519,6 +589,8 @@ def filter_pairs(handle: _lib.Handle, cols1: RecordColumns, cols2: RecordColumns
         b1, e1, b2, e2, keep, p_stats, insert = pair_plan(handle, cols1, cols2, plans[0], plans[1], pair_min_overlap, pair_max_mismatches,
                                                           pair_max_error_permille, rules.get("min_length", 1), return_insert=True)
         stats["pair"] = p_stats
+        if dedup:
+            keep, stats["dedup"] = dedup_plan(handle, cols1, cols2, b1, e1, b2, e2, keep, dedup_key_bases, dedup_prefer)
         merged, flag, stats["merge"] = merge_pairs(handle, cols1, cols2, b1, e1, b2, e2, keep, insert, pair_min_overlap, pair_max_mismatches,
                                                    pair_max_error_permille, merge_quality_cap, titles=titles)
         keep = keep & (flag ^ 1)                             # both hold 0 / 1
@@ -529,6 +601,8 @@ def filter_pairs(handle: _lib.Handle, cols1: RecordColumns, cols2: RecordColumns
     else:
         (b1, e1, k1), (b2, e2, k2) = plans
         keep = ((k1 != 0) & (k2 != 0)).to(torch.uint8)
+    if dedup and not merge:
+        keep, stats["dedup"] = dedup_plan(handle, cols1, cols2, b1, e1, b2, e2, keep, dedup_key_bases, dedup_prefer)
     if profile:
         for name, cols, b, e in (("read1", cols1, b1, e1), ("read2", cols2, b2, e2)):
             before = profile_columns(handle, cols)

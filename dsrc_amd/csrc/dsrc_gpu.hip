@@ -50,6 +50,7 @@
 #include "k_columns_adapt.h"
 #include "k_columns_pair.h"
 #include "k_columns_merge.h"
+#include "k_columns_dedup.h"
 #include "k_columns_profile.h"
 
 namespace
@@ -2471,6 +2472,75 @@ int dsrcgpu_columns_pair_plan(dsrcgpu_handle* h, const dsrcgpu_columns_in* in1, 
 			return fail(h, rc, "pair plan, read %u: %s", side + 1, why.c_str());
 		}
 	for (u32 k = 0; k < PAIR_N_STATS; ++k) stats[k] = res[k + 2];
+	return DSRCGPU_OK;
+}
+
+// the dedup plan (k_columns_dedup.h): the check pass per side as in the pair plan (one side: the second error word stays clean), the
+// table filled by hipMemsetAsync, then the three launches; the error words and the statistics come home in one copy
+int dsrcgpu_columns_dedup_plan(dsrcgpu_handle* h, const dsrcgpu_columns_in* in1, const dsrcgpu_columns_in* in2, const dsrcgpu_dedup_rules* rules,
+							   const uint64_t* d_begin1, const uint64_t* d_end1, const uint64_t* d_begin2, const uint64_t* d_end2,
+							   const uint8_t* d_keep_in, uint8_t* d_keep, uint64_t* d_dup_of, uint64_t* d_copies, uint64_t stats[24])
+{
+	if (!h) return DSRCGPU_E_ARG;
+	if (!rules || !stats) return fail(h, DSRCGPU_E_ARG, "null argument");
+	for (u32 k = 0; k < DEDUP_N_STATS; ++k) stats[k] = 0;
+	const bool two = in2 != nullptr;
+	const bool quals = rules->prefer == 1;               // the qualities are read for the rank of prefer = 1 only
+	ColIn c1, c2{};
+	{ const int rc = sel_in_args(h, in1, false, c1, quals); if (rc) return rc; }
+	if (two) { const int rc = sel_in_args(h, in2, false, c2, quals); if (rc) return rc; }
+	if (two && c1.n_recs != c2.n_recs) return fail(h, DSRCGPU_E_ARG, "dedup plan: %llu records of read 1, %llu of read 2", (unsigned long long)c1.n_recs, (unsigned long long)c2.n_recs);
+	if (c1.n_recs > (1ull << 31)) return fail(h, DSRCGPU_E_ARG, "dedup plan: more than 2^31 records in one call");
+	if (rules->prefer > 1) return fail(h, DSRCGPU_E_ARG, "dedup rules: prefer must be 0 (first) or 1 (best quality)");
+	if (rules->hash_bits > 64) return fail(h, DSRCGPU_E_ARG, "dedup rules: hash_bits above 64");
+	if (rules->reserved[0] | rules->reserved[1] | rules->reserved[2] | rules->reserved[3] | rules->reserved[4]) return fail(h, DSRCGPU_E_ARG, "dedup rules: reserved fields must be 0");
+	if (!d_begin1 != !d_end1) return fail(h, DSRCGPU_E_ARG, "columns: d_begin1 and d_end1 go together");
+	if (!d_begin2 != !d_end2) return fail(h, DSRCGPU_E_ARG, "columns: d_begin2 and d_end2 go together");
+	if (!two && d_begin2) return fail(h, DSRCGPU_E_ARG, "dedup plan: ranges of read 2 without in2");
+	if (c1.n_recs == 0) return DSRCGPU_OK;
+	if (!d_keep) return fail(h, DSRCGPU_E_ARG, "null argument");
+	HIPCHK(hipSetDevice(h->device));
+	hipStream_t s = h->stream;
+	const u64 R = c1.n_recs;
+	u64 M = 2;
+	while (M < 2 * R) M <<= 1;                           // at most half the slots are ever claimed: a probe always ends
+	const size_t n_res = 2 + DEDUP_N_STATS;
+	const size_t slot_bytes = (size_t)(quals ? 20 : 16);     // occ 4, best 8, count 4, low 4 under prefer = 1
+	{ const int rc = ensure_arena(h, n_res * 8 + (size_t)R * 20 + (size_t)M * slot_bytes + 8 * 256 + 1024); if (rc) return rc; }
+	const size_t o_res = h->arena.alloc(n_res * 8), o_hash = h->arena.alloc((size_t)R * 8), o_rank = h->arena.alloc((size_t)R * 8), o_slot = h->arena.alloc((size_t)R * 4),
+	             o_occ = h->arena.alloc((size_t)M * 4), o_best = h->arena.alloc((size_t)M * 8), o_count = h->arena.alloc((size_t)M * 4),
+	             o_low = quals ? h->arena.alloc((size_t)M * 4) : 0;
+	if (h->arena.failed) return fail(h, DSRCGPU_E_NOMEM, "arena exhausted (dedup plan)");
+	u64* d_res = AP<u64>(h, o_res);                      // an error word per side, the 24 statistics
+	const DedupTable t{AP<u32>(h, o_occ), AP<u64>(h, o_best), AP<u32>(h, o_count), quals ? AP<u32>(h, o_low) : nullptr, M - 1};
+	HIPCHK(hipMemsetAsync(d_res, 0xFF, 2 * 8, s));
+	HIPCHK(hipMemsetAsync(d_res + 2, 0, DEDUP_N_STATS * 8, s));
+	HIPCHK(hipMemsetAsync(t.occ, 0xFF, (size_t)M * 4, s));
+	HIPCHK(hipMemsetAsync(t.best, 0, (size_t)M * 8, s));
+	HIPCHK(hipMemsetAsync(t.count, 0, (size_t)M * 4, s));
+	if (quals) HIPCHK(hipMemsetAsync(t.low, 0xFF, (size_t)M * 4, s));
+	const AdaptPlanIn w1{d_begin1, d_end1, nullptr}, w2{d_begin2, d_end2, nullptr};
+	const u32 bits = rules->hash_bits;
+	const DedupIn in{c1, c2, w1, w2, d_keep_in, rules->key_bases, bits == 0 || bits == 64 ? ~0ull : (1ull << bits) - 1ull, two ? 1u : 0u, rules->prefer};
+	const u64 wpg = WG / 64;
+	const dim3 g_check((u32)std::max<u64>(1, std::min<u64>(1024, (R + WG - 1) / WG)));
+	const dim3 g_wave((u32)std::max<u64>(1, std::min<u64>(4096, (R + wpg - 1) / wpg)));
+	hipLaunchKernelGGL(k_adapt_check, g_check, dim3(WG), 0, s, c1, w1, d_res); KCHK();
+	if (two) { hipLaunchKernelGGL(k_adapt_check, g_check, dim3(WG), 0, s, c2, w2, d_res + 1); KCHK(); }
+	hipLaunchKernelGGL(k_dedup_key, g_wave, dim3(WG), 0, s, in, AP<u64>(h, o_hash), AP<u64>(h, o_rank), d_res + 2, d_res); KCHK();
+	hipLaunchKernelGGL(k_dedup_insert, g_wave, dim3(WG), 0, s, in, AP<u64>(h, o_hash), AP<u64>(h, o_rank), t, AP<u32>(h, o_slot), d_res); KCHK();
+	hipLaunchKernelGGL(k_dedup_resolve, g_check, dim3(WG), 0, s, d_keep_in, R, t, AP<u32>(h, o_slot), rules->prefer, d_keep, d_dup_of, d_copies, d_res + 2, d_res); KCHK();
+	u64 res[2 + DEDUP_N_STATS];
+	HIPCHK(hipMemcpyAsync(res, d_res, sizeof(res), hipMemcpyDeviceToHost, s));
+	HIPCHK(hipStreamSynchronize(s));
+	for (u32 side = 0; side < 2; ++side)
+		if (res[side] != COLE_NONE)
+		{
+			const int rc = sel_input_error(h, res[side]);
+			const std::string why = dsrcgpu_last_error(h);
+			return fail(h, rc, "dedup plan, read %u: %s", side + 1, why.c_str());
+		}
+	for (u32 k = 0; k < DEDUP_N_STATS; ++k) stats[k] = res[k + 2];
 	return DSRCGPU_OK;
 }
 

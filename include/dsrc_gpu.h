@@ -358,6 +358,65 @@ int dsrcgpu_columns_pair_plan(dsrcgpu_handle* h, const dsrcgpu_columns_in* in1, 
 		uint64_t* d_insert                                                                  /* device, n_records, may be NULL */,
 		uint64_t stats[11]);
 
+/* dsrcgpu_columns_dedup_plan: the fourth planner -- exact duplicate reads, or exact duplicate pairs, are marked, and the keep flag
+ * that comes out leaves one record of every set of equal ones.  It feeds dsrcgpu_columns_select_device, dsrcgpu_columns_profile,
+ * dsrcgpu_columns_merge_device and the encoder like any other keep flag.  The first columnar call whose records talk to each other:
+ * a device-wide hash table built with returning atomics (dsrc_amd/csrc/k_columns_dedup.h); the result does not depend on the order in
+ * which the records reach the table.
+ * Conventions as dsrcgpu_columns_pair_plan: the handle's own lane and stream, scratch from the arena (about 28 bytes a record and 16 to
+ * 20 a table slot, 2 to 4 slots a record), synchronised before it returns, codec state left alone, a colour-space handle:
+ * DSRCGPU_E_ARG.  in2 == NULL: single-end.  With in2, record r of `in2` is the mate of record r of `in1` and a pair is ONE record with
+ * a key of two parts.  Of each side only d_bases, d_seq_offs and -- under prefer = 1 -- d_quals are read; d_titles and d_title_offs may
+ * be NULL, and so may d_quals under prefer = 0.
+ * The plan in: per side d_begin<s> / d_end<s> (both NULL = whole reads; one without the other: DSRCGPU_E_ARG; the two sides are
+ * independent of each other) and ONE d_keep_in (NULL = every record; any non-zero byte keeps).  A record is CONSIDERED iff d_keep_in is
+ * NULL or d_keep_in[r] != 0.
+ * The key of record r: per side s, [b_s, e_s) its range, n_s = e_s - b_s, k_s = key_bases ? min(n_s, key_bases) : n_s; the key is the
+ * tuple (k_1, bases1[b_1 .. b_1 + k_1)) and, with two sides, it goes on with (k_2, bases2[b_2 .. b_2 + k_2)).  Two records are
+ * duplicates iff their keys are equal, compared as bytes: code 4 equals code 4 and 255 equals 255, the lengths are part of the key (a
+ * read is no duplicate of its own prefix), there is no reverse complement and no mismatch tolerance.  A key is EMPTY when it holds no
+ * base (k_1 + k_2 == 0); all considered records with an empty key are duplicates of each other.
+ * The rank of record r is the pair (q, -r), compared q first: q = 0 under prefer = 0; under prefer = 1, q = min(2^32 - 1, the sum of the
+ * qualities at the key positions of both sides).
+ *   classes = {}                                                 (key -> the considered records that have it)
+ *   for r = 0 .. n_records - 1:
+ *     if not considered(r): d_keep[r] = 0, d_dup_of[r] = 2^64 - 1, d_copies[r] = 0, next r
+ *     classes[key(r)] += r
+ *   for every class C: rep = the member of highest rank       (prefer = 0: the lowest index; prefer = 1: the highest q, lowest index on a tie)
+ *     for r in C: d_keep[r] = (r == rep), d_dup_of[r] = rep, d_copies[r] = (r == rep) ? |C| : 0
+ * d_dup_of and d_copies may be NULL, each on its own.  d_keep may be the very pointer d_keep_in: a record's incoming flag is read
+ * before its outgoing one is written, and no other record's is touched.  In every other way the outputs must not overlap the inputs
+ * or the arrays of `in1` / `in2`; this is not checked.
+ * Not done here: reverse-complement or mismatch-tolerant duplicates, optical or UMI duplicates, duplicates across calls (every call
+ * starts with an empty table), any check of the titles.
+ * stats (host): [0] records considered, [1] records kept = the number of classes, [2] records dropped as duplicates ([0] = [1] + [2]),
+ * [3] classes of two and more members, [4] the size of the largest class, [5] records that came in dropped, [6] considered records whose
+ * key is empty, [7] classes whose representative is not their lowest index (0 under prefer = 0), [8 .. 23] the duplication-level
+ * histogram over classes in FastQC's bins: sizes 1, 2, .., 9, 10-49, 50-99, 100-499, 500-999, 1000-4999, 5000-9999, >= 10000; their
+ * sum is [1].
+ * n_records == 0: DSRCGPU_OK, stats 0.
+ * DSRCGPU_E_ARG, nothing written: in2 with another record count than in1; n_records > 2^31 (refused before anything is read); prefer
+ * above 1; hash_bits above 64; a non-zero reserved field; a half-given range pair; ranges of side 2 without in2; a null d_keep or stats.
+ * DSRCGPU_E_INPUT (outputs untouched), for considered and dropped records alike: the conditions of dsrcgpu_columns_adapter_plan on either
+ * side; dsrcgpu_last_error names the side (read 1 is reported first), the lowest record of that side and the reason.  No input makes a
+ * kernel read outside the caller's arrays. */
+typedef struct dsrcgpu_dedup_rules
+{
+	uint32_t key_bases;             /* 0 = the whole range, else at most this many leading bases of each side's range */
+	uint32_t prefer;                /* 0 = the first record of a class is kept, 1 = the one with the highest quality sum */
+	uint32_t hash_bits;             /* a diagnostic: 0 or 64 = the full hash, 1 .. 63 = only that many low bits of it are used.  The
+	                                   results never depend on it; few bits make different keys meet in the table (long probes, slow) */
+	uint32_t reserved[5];           /* must be 0 */
+} dsrcgpu_dedup_rules;
+
+int dsrcgpu_columns_dedup_plan(dsrcgpu_handle* h, const dsrcgpu_columns_in* in1, const dsrcgpu_columns_in* in2   /* may be NULL */,
+		const dsrcgpu_dedup_rules* rules,
+		const uint64_t* d_begin1, const uint64_t* d_end1, const uint64_t* d_begin2, const uint64_t* d_end2   /* device, may be NULL */,
+		const uint8_t* d_keep_in                                                                             /* device, may be NULL */,
+		uint8_t* d_keep                                                                                      /* device, n_records: 1 / 0 */,
+		uint64_t* d_dup_of, uint64_t* d_copies                                                               /* device, n_records each, may be NULL */,
+		uint64_t stats[24]);
+
 /* dsrcgpu_columns_merge_device: what the insert size of the pair plan is for -- the two mates of a short insert become ONE read with
  * a consensus where they overlap (fastp --merge, PEAR, FLASH, BBMerge).  The first columnar call that writes new bases and qualities
  * instead of copying ranges.  It takes the pair plan's outputs -- the ranges, the pair's keep flag and d_insert -- and writes the merged
@@ -472,7 +531,8 @@ int dsrcgpu_columns_merge_device(dsrcgpu_handle* h, const dsrcgpu_columns_in* in
  * file give what one call on all of it gives.  totals (host) is this call's own tot[8] either way.  Everything is an integer sum: the
  * result does not depend on the order in which the device takes the records and is bit-reproducible; no counter wraps below 2^64.
  * n_records == 0: DSRCGPU_OK, totals 0, d_profile zeroed if accumulate == 0 and untouched otherwise.
- * Not done here: k-mer counts, a duplication estimate, over-represented sequences, per-tile quality (nothing here reads the titles),
+ * Not done here: k-mer counts, a duplication estimate (dsrcgpu_columns_dedup_plan has the duplication levels), over-represented
+ * sequences, per-tile quality (nothing here reads the titles),
  * a per-cycle quality HISTOGRAM (per cycle there is the sum and the count, so the mean, not the quartiles).
  * On any error d_profile is untouched.  DSRCGPU_E_ARG: n_cycles 0 or above DSRCGPU_PROFILE_MAX_CYCLES; accumulate above 1; a non-zero
  * reserved field; a half-given range pair; a null d_profile, rules or totals; a null in->d_quals (or d_bases) with bases_len > 0.
