@@ -28,6 +28,7 @@ EXPORTS = [
     "dsrcgpu_decompress_batch_columns_device", "dsrcgpu_compress_columns_device", "dsrcgpu_columns_cut",
     "dsrcgpu_columns_trim_plan", "dsrcgpu_columns_select_device", "dsrcgpu_columns_adapter_plan", "dsrcgpu_columns_pair_plan",
     "dsrcgpu_columns_profile", "dsrcgpu_columns_merge_device", "dsrcgpu_columns_dedup_plan",
+    "dsrcgpu_columns_kmer_count", "dsrcgpu_kmer_table_merge", "dsrcgpu_kmer_spectrum", "dsrcgpu_kmer_lookup",
 ]
 
 # error codes of include/dsrc_gpu.h that callers tell apart (DsrcGpuError.code)
@@ -169,6 +170,33 @@ PROFILE_TOTALS = ("records", "bases", "bases_q20", "bases_q30", "quality_sum", "
 def profile_words(n_cycles: int) -> int:
     """DSRCGPU_PROFILE_WORDS: the uint64 words of a profile of n_cycles cycles."""
     return 11 * n_cycles + 622
+
+
+class KmerRules(C.Structure):
+    """dsrcgpu_kmer_rules: KmerRules(k, canonical, accumulate, hash_bits, capacity); hash_bits is a diagnostic (0 or 64: the full
+    hash).  The library is the one that refuses figures out of range."""
+    _fields_ = [("k", C.c_uint32), ("canonical", C.c_uint32), ("accumulate", C.c_uint32), ("hash_bits", C.c_uint32), ("capacity", C.c_uint64),
+                ("reserved", C.c_uint32 * 4)]
+
+    def __init__(self, k=21, canonical=1, accumulate=0, hash_bits=0, capacity=16, reserved=(0, 0, 0, 0)):
+        super().__init__()
+        self.k, self.canonical, self.accumulate, self.hash_bits, self.capacity = k, canonical, accumulate, hash_bits, capacity
+        self.reserved = (C.c_uint32 * 4)(*reserved)
+
+
+KMER_MAX_K = 31                  # DSRCGPU_KMER_MAX_K
+KMER_PROBE_LIMIT = 1024          # DSRCGPU_KMER_PROBE_LIMIT
+KMER_MAX_BINS = 65536            # DSRCGPU_KMER_MAX_BINS
+KMER_EMPTY = 0xFFFFFFFFFFFFFFFF  # the key word of a free slot
+KMER_STATS = ("records_considered", "records_came_dropped", "records_short", "windows", "kmers_counted", "windows_broken", "kmers_new", "overflow",
+              "distinct_after", "total_after")
+KMER_MERGE_STATS = ("keys_merged", "keys_new", "occurrences_added", "overflow", "distinct_after", "total_after")
+KMER_SPECTRUM_TOTALS = ("distinct", "occurrences", "singletons", "largest_count")
+
+
+def kmer_words(capacity: int) -> int:
+    """DSRCGPU_KMER_WORDS: the uint64 words of a k-mer table of `capacity` slots."""
+    return 8 + 2 * capacity
 
 
 class HostColumns(typing.NamedTuple):
@@ -566,6 +594,45 @@ class Handle:
         self._chk(self.L.dsrcgpu_columns_profile(self.h, C.byref(cols_in), C.c_void_p(d_begin), C.c_void_p(d_end), C.c_void_p(d_keep),
                                                  C.byref(rules), C.c_void_p(d_profile), totals))
         return list(totals)
+
+    def _chk_need(self, rc, need):
+        if rc < 0:
+            e = DsrcGpuError(rc, self.L.dsrcgpu_last_error(self.h).decode())
+            e.need = int(need[0]) if rc == E_CAPACITY else None
+            raise e
+
+    def columns_kmer_count(self, cols_in: ColumnsIn, d_begin, d_end, d_keep, rules: KmerRules, d_table: int):
+        """dsrcgpu_columns_kmer_count: the k-mers of the records of `cols_in` under the plan d_begin / d_end / d_keep (device
+        addresses or None: whole reads, every record) into the table d_table (device memory of kmer_words(rules.capacity) uint64
+        words; initialised first, or added to with rules.accumulate = 1).  Returns the sixteen statistics (KMER_STATS names the
+        first ten); DsrcGpuError.code == E_CAPACITY when the table is too small for the call -- `need` of the exception then holds
+        the capacity that would do, and the table is untouched."""
+        stats, need = (C.c_uint64 * 16)(), (C.c_uint64 * 1)()
+        self._chk_need(self.L.dsrcgpu_columns_kmer_count(self.h, C.byref(cols_in), C.c_void_p(d_begin), C.c_void_p(d_end), C.c_void_p(d_keep),
+                                                         C.byref(rules), C.c_void_p(d_table), stats, need), need)
+        return list(stats)
+
+    def kmer_table_merge(self, d_src: int, d_dst: int):
+        """dsrcgpu_kmer_table_merge: every (key, count) of the table at d_src is added into the table at d_dst (same k and
+        canonical, any capacities).  Returns the eight statistics (KMER_MERGE_STATS names the first six); E_CAPACITY as
+        columns_kmer_count."""
+        stats, need = (C.c_uint64 * 8)(), (C.c_uint64 * 1)()
+        self._chk_need(self.L.dsrcgpu_kmer_table_merge(self.h, C.c_void_p(d_src), C.c_void_p(d_dst), stats, need), need)
+        return list(stats)
+
+    def kmer_spectrum(self, d_table: int, n_bins: int, d_hist: int):
+        """dsrcgpu_kmer_spectrum: d_hist[c] (device memory of n_bins uint64 words) = the distinct keys counted c times, the last bin
+        folding.  Returns the four totals (KMER_SPECTRUM_TOTALS names them)."""
+        totals = (C.c_uint64 * 4)()
+        self._chk(self.L.dsrcgpu_kmer_spectrum(self.h, C.c_void_p(d_table), C.c_uint32(n_bins), C.c_void_p(d_hist), totals))
+        return list(totals)
+
+    def kmer_lookup(self, d_table: int, d_kmers, n: int, d_counts) -> int:
+        """dsrcgpu_kmer_lookup: d_counts[i] = the count of the packed k-mer d_kmers[i] (device memory of n uint64 words each).
+        Returns the number of query words of 4^k and more."""
+        invalid = C.c_uint64()
+        self._chk(self.L.dsrcgpu_kmer_lookup(self.h, C.c_void_p(d_table), C.c_void_p(d_kmers), C.c_uint64(n), C.c_void_p(d_counts), C.byref(invalid)))
+        return invalid.value
 
     def columns_select_device(self, cols_in: ColumnsIn, d_begin, d_end, d_keep, out: Columns, d_source=None):
         """dsrcgpu_columns_select_device: the kept records of `cols_in`, cut to [begin, end), compacted into the device arrays `out`

@@ -2,7 +2,8 @@
 (dsrcgpu_compress_columns_device), and what runs between the two: trim_plan (dsrcgpu_columns_trim_plan), adapter_plan
 (dsrcgpu_columns_adapter_plan), pair_plan (dsrcgpu_columns_pair_plan), dedup_plan (dsrcgpu_columns_dedup_plan), merge_pairs
 (dsrcgpu_columns_merge_device), select_columns (dsrcgpu_columns_select_device), filter_columns and, for paired-end data,
-filter_pairs, and the report on either side of them, profile_columns (dsrcgpu_columns_profile), include/dsrc_gpu.h.
+filter_pairs, the report on either side of them, profile_columns (dsrcgpu_columns_profile), and the k-mer table of a plan, count_kmers
+and KmerTable (dsrcgpu_columns_kmer_count, dsrcgpu_kmer_table_merge, dsrcgpu_kmer_spectrum, dsrcgpu_kmer_lookup), include/dsrc_gpu.h.
 
 The blocks are already in device memory; the arrays are allocated by torch on the same device and filled by the library's
 kernels -- no text, no host round trip of the payload.  With the emulator build of the library (tests/emu) device pointers
@@ -339,7 +340,7 @@ def profile_columns(handle: _lib.Handle, cols: RecordColumns, begin=None, end=No
 
 def filter_columns(handle: _lib.Handle, cols: RecordColumns, titles: bool = True, adapters=None, adapter_min_overlap: int = 3,
                    adapter_max_error_permille: int = 100, profile: bool = False, dedup: bool = False, dedup_key_bases: int = 0,
-                   dedup_prefer: str = "first", **rules):
+                   dedup_prefer: str = "first", kmers=None, **rules):
     """trim_plan(**rules) and select_columns with its plan in sequence: -> (RecordColumns of the trimmed, kept records, stats).
     adapters (see adapter_plan): between the two, adapter_plan narrows the trim plan -- the quality trim first, the adapter second,
     the order of cutadapt and fastp -- with the same min_length; stats is then the trim plan's dict plus a key "adapter" that holds
@@ -349,9 +350,13 @@ def filter_columns(handle: _lib.Handle, cols: RecordColumns, titles: bool = True
     that come out -- taken from the final plan on `cols`, with the same n_cycles.
     dedup=True: last among the plans, dedup_plan(key_bases=dedup_key_bases, prefer=dedup_prefer) on the final ranges and keep leaves one
     record of every set of exact duplicates; stats gets "dedup", its dict, the number of records that come out is
-    stats["dedup"]["records_kept"], and "profile_after" reflects it."""
+    stats["dedup"]["records_kept"], and "profile_after" reflects it.
+    kmers=k (an int, 1 .. 31): stats gets "kmers_after", the KmerTable of count_kmers(k) under the final plan on `cols` -- the
+    canonical k-mers of the records that come out, and it needs no select."""
     if adapters is not None:
         codes = _adapter_codes(adapters)
+    if kmers is not None:
+        _check_int("kmers", kmers, 1, _lib.KMER_MAX_K)
     if dedup:
         _check_dedup_args(dedup_key_bases, dedup_prefer)
     begin, end, keep, stats = trim_plan(handle, cols, **rules)
@@ -365,6 +370,8 @@ def filter_columns(handle: _lib.Handle, cols: RecordColumns, titles: bool = True
     if profile:
         before = profile_columns(handle, cols)
         stats = dict(stats, profile_before=before, profile_after=profile_columns(handle, cols, begin, end, keep, n_cycles=before.n_cycles))
+    if kmers is not None:
+        stats = dict(stats, kmers_after=count_kmers(handle, cols, kmers, begin, end, keep)[0])
     return select_columns(handle, cols, begin, end, keep, titles=titles), stats
 
 
@@ -552,7 +559,7 @@ def merge_pairs(handle: _lib.Handle, cols1: RecordColumns, cols2: RecordColumns,
 def filter_pairs(handle: _lib.Handle, cols1: RecordColumns, cols2: RecordColumns, titles: bool = True, adapters1=None, adapters2=None,
                  overlap: bool = True, pair_min_overlap: int = 30, pair_max_mismatches: int = 5, pair_max_error_permille: int = 200,
                  adapter_min_overlap: int = 3, adapter_max_error_permille: int = 100, profile: bool = False, merge: bool = False,
-                 merge_quality_cap: int = 41, dedup: bool = False, dedup_key_bases: int = 0, dedup_prefer: str = "first", **rules):
+                 merge_quality_cap: int = 41, dedup: bool = False, dedup_key_bases: int = 0, dedup_prefer: str = "first", kmers=None, **rules):
     """filter_columns for paired-end data: per side trim_plan(**rules) and, if adapters<s> is given, adapter_plan; then pair_plan with
     the same min_length, which cuts read-through found from the overlap of the mates and decides per PAIR; then one select_columns per
     side with that side's ranges and the joint keep -> (out1, out2, stats), out1.n_records == out2.n_records always and record j of
@@ -567,9 +574,14 @@ def filter_pairs(handle: _lib.Handle, cols1: RecordColumns, cols2: RecordColumns
     out1.n_records is the pair plan's pairs_kept, and "profile_after" is that of out1 / out2.
     dedup=True: behind the pair plan (overlap=False: on keep1 & keep2) and in front of the merge, dedup_plan(key_bases=dedup_key_bases,
     prefer=dedup_prefer) keyed on BOTH mates' final ranges leaves one pair of every set of exact duplicate pairs; stats["dedup"] is its
-    dict, the pairs that come out -- merged ones included -- number stats["dedup"]["records_kept"], and "profile_after" reflects it."""
+    dict, the pairs that come out -- merged ones included -- number stats["dedup"]["records_kept"], and "profile_after" reflects it.
+    kmers=k (an int, 1 .. 31): stats gets "kmers_after", ONE KmerTable with the canonical k-mers of both sides under the final
+    ranges and the final keep -- count_kmers(k) on read 1, then on read 2 into the same table; of the mates out1 / out2, so under
+    merge=True without the merged reads."""
     if dedup:
         _check_dedup_args(dedup_key_bases, dedup_prefer)
+    if kmers is not None:
+        _check_int("kmers", kmers, 1, _lib.KMER_MAX_K)
     _check_pair_args(cols1, cols2, pair_min_overlap, pair_max_mismatches, pair_max_error_permille, rules.get("min_length", 1))
     if merge:
         if not overlap:
@@ -607,6 +619,198 @@ def filter_pairs(handle: _lib.Handle, cols1: RecordColumns, cols2: RecordColumns
         for name, cols, b, e in (("read1", cols1, b1, e1), ("read2", cols2, b2, e2)):
             before = profile_columns(handle, cols)
             stats[name] = dict(stats[name], profile_before=before, profile_after=profile_columns(handle, cols, b, e, keep, n_cycles=before.n_cycles))
+    if kmers is not None:
+        table, _ = count_kmers(handle, cols1, kmers, b1, e1, keep)
+        stats["kmers_after"], _ = count_kmers(handle, cols2, kmers, b2, e2, keep, into=table)
     out1 = select_columns(handle, cols1, b1, e1, keep, titles=titles)
     out2 = select_columns(handle, cols2, b2, e2, keep, titles=titles)
     return (out1, out2, merged, stats) if merge else (out1, out2, stats)
+
+
+# ---- k-mer count (dsrcgpu_columns_kmer_count and the three calls on its table) ---------------------------------------------------------
+def _check_kmer_capacity(capacity):
+    _check_int("capacity", capacity, 16, 1 << 40)
+    if capacity & (capacity - 1):
+        raise ValueError("capacity must be a power of two")
+
+
+def pack_kmers(kmers, k: int):
+    """Strings of k letters A C G T -> a list of packed forward words (first base most significant)."""
+    out = []
+    for s in kmers:
+        if not isinstance(s, str) or len(s) != k or any(ch not in _BASE_CODES for ch in s.upper()):
+            raise ValueError("a k-mer is a string of %d letters A C G T" % k)
+        v = 0
+        for ch in s.upper():
+            v = (v << 2) | _BASE_CODES[ch]
+        out.append(v)
+    return out
+
+
+def unpack_kmer(word: int, k: int) -> str:
+    return "".join("ACGT"[(word >> (2 * (k - 1 - j))) & 3] for j in range(k))
+
+
+@dataclasses.dataclass
+class KmerTable:
+    """A table of dsrcgpu_columns_kmer_count: one int64 tensor of _lib.kmer_words(capacity) words on the device of the columns
+    (layout: include/dsrc_gpu.h; the EMPTY key reads as -1) and views of its parts.  Slot order is unspecified; items() is the
+    table's content.  Nothing crosses to the host but by summary(), top() and the totals of spectrum()."""
+    data: torch.Tensor
+    k: int
+    canonical: bool
+
+    @property
+    def capacity(self) -> int:
+        return (self.data.numel() - 8) // 2
+
+    @property
+    def keys(self):
+        return self.data[8: 8 + self.capacity]
+
+    @property
+    def counts(self):
+        return self.data[8 + self.capacity:]
+
+    @staticmethod
+    def empty(handle: _lib.Handle, k: int, canonical: bool = True, capacity: int = 16, device="cpu") -> "KmerTable":
+        """An initialised table without a key (a count over no records)."""
+        _check_int("k", k, 1, _lib.KMER_MAX_K)
+        _check_kmer_capacity(capacity)
+        t = KmerTable(torch.empty(_lib.kmer_words(capacity), dtype=torch.int64, device=device), k, bool(canonical))
+        _quiesce(t.data.device)
+        handle.columns_kmer_count(_lib.ColumnsIn(), None, None, None, _lib.KmerRules(k, int(bool(canonical)), 0, 0, capacity), t.data.data_ptr())
+        return t
+
+    def summary(self) -> dict:
+        """The header as a dict of ints -- the only part that crosses to the host."""
+        h = self.data[:8].tolist()
+        return dict(k=self.k, canonical=self.canonical, capacity=h[1], distinct=h[2], occurrences=h[3], overflow=h[4])
+
+    def items(self):
+        """-> (keys, counts) of the occupied slots, sorted by key: int64 tensors on the table's device."""
+        keys, counts = self.keys, self.counts
+        used = keys != -1
+        keys, order = torch.sort(keys[used])
+        return keys, counts[used][order]
+
+    def top(self, n: int):
+        """The n most frequent k-mers as a list of (string, count), the highest count first, equal counts by key."""
+        _check_int("n", n, 0, 1 << 40)
+        keys, counts = self.items()
+        n = min(n, keys.numel())
+        if n == 0:
+            return []
+        floor = torch.topk(counts, n).values[-1]
+        cand = counts >= floor                               # every key that ties with the n-th is a candidate: the cut is by key, not by slot
+        keys, counts = keys[cand], counts[cand]
+        order = torch.sort(counts, descending=True, stable=True).indices[:n]
+        return [(unpack_kmer(key, self.k), c) for key, c in zip(keys[order].tolist(), counts[order].tolist())]
+
+    def spectrum(self, handle: _lib.Handle, n_bins: int = 256):
+        """dsrcgpu_kmer_spectrum -> (hist, totals): hist[c] = the distinct keys counted c times (int64, n_bins, the last bin folds),
+        totals a dict with the keys of _lib.KMER_SPECTRUM_TOTALS."""
+        _check_int("n_bins", n_bins, 2, _lib.KMER_MAX_BINS)
+        hist = torch.empty(n_bins, dtype=torch.int64, device=self.data.device)
+        _quiesce(self.data.device)
+        totals = handle.kmer_spectrum(self.data.data_ptr(), n_bins, hist.data_ptr())
+        return hist, dict(zip(_lib.KMER_SPECTRUM_TOTALS, totals))
+
+    def lookup(self, handle: _lib.Handle, kmers, return_invalid: bool = False):
+        """dsrcgpu_kmer_lookup: the count of each k-mer -- strings of k letters, or an int64 tensor of packed forward words on the
+        table's device -> int64 counts on that device, 0 for a key that is absent (with return_invalid: and the number of words of
+        4^k and more).  Under a canonical table a k-mer and its reverse complement give the same count."""
+        device = self.data.device
+        if not isinstance(kmers, torch.Tensor):
+            kmers = torch.tensor(pack_kmers(list(kmers), self.k), dtype=torch.int64, device=device)
+        if kmers.dtype != torch.int64 or kmers.dim() != 1 or kmers.device != device:
+            raise ValueError("kmers is a list of strings or a one-dimensional int64 tensor on the table's device")
+        kmers = kmers.contiguous()
+        out = torch.empty(kmers.numel(), dtype=torch.int64, device=device)
+        _quiesce(device)
+        invalid = handle.kmer_lookup(self.data.data_ptr(), kmers.data_ptr() if kmers.numel() else None, kmers.numel(),
+                                     out.data_ptr() if kmers.numel() else None)
+        return (out, invalid) if return_invalid else out
+
+    def merged_into(self, handle: _lib.Handle, other: "KmerTable") -> "KmerTable":
+        """dsrcgpu_kmer_table_merge: every (key, count) of this table is added into `other` (same k and canonical, any capacity),
+        which is returned.  If `other` is too small it is grown first (its tensor is replaced)."""
+        if not isinstance(other, KmerTable) or other.k != self.k or other.canonical != self.canonical or other.data.device != self.data.device:
+            raise ValueError("both tables hold the same k and canonical on one device")
+        if other.data.data_ptr() == self.data.data_ptr():
+            raise ValueError("a table cannot be merged into itself")
+        _quiesce(self.data.device)
+        try:
+            stats = handle.kmer_table_merge(self.data.data_ptr(), other.data.data_ptr())
+        except _lib.DsrcGpuError as e:
+            if e.code != _lib.E_CAPACITY:
+                raise
+            other.data = other.grown(handle, e.need).data
+            stats = handle.kmer_table_merge(self.data.data_ptr(), other.data.data_ptr())
+        if stats[3]:
+            raise RuntimeError("k-mer merge: %d occurrences lost to overflow" % stats[3])
+        return other
+
+    def grown(self, handle: _lib.Handle, capacity: int) -> "KmerTable":
+        """A new table of `capacity` slots with every (key, count) of this one."""
+        new = KmerTable.empty(handle, self.k, self.canonical, capacity, self.data.device)
+        return self.merged_into(handle, new)
+
+
+def count_kmers(handle: _lib.Handle, cols: RecordColumns, k: int, begin=None, end=None, keep=None, canonical: bool = True, capacity=None,
+                into=None):
+    """dsrcgpu_columns_kmer_count on the records of `cols` under the plan begin / end / keep (None: whole reads, every record; as the
+    planners return them) -> (KmerTable, stats), stats a dict with the keys of _lib.KMER_STATS.  Every window of k bases A C G T of a
+    considered record's range counts once under its key: the lower of the forward word and its reverse complement (canonical=False:
+    the forward word).  capacity=None: a first call sizes the table (a power of two of at least twice the windows); a capacity
+    that is too small raises DsrcGpuError with .code == E_CAPACITY and .need.  into: an earlier KmerTable of the same k and
+    canonical on the same device -- the counts are added to it and it is returned (the mates of a pair, the batches of a file); if
+    it is too small it is grown to the size the library asks for (its tensor is replaced).  A non-zero overflow raises RuntimeError:
+    with the full hash it is not expected.  Arguments out of range raise ValueError before the library is called.  Nothing of the
+    payload crosses to the host."""
+    device = cols.bases.device
+    R = cols.n_records
+    _check_int("k", k, 1, _lib.KMER_MAX_K)
+    canonical = bool(canonical)
+    if into is not None:
+        if not isinstance(into, KmerTable) or into.k != k or into.canonical != canonical or capacity not in (None, into.capacity):
+            raise ValueError("into is an earlier KmerTable with the same k and canonical")
+        if into.data.dtype != torch.int64 or into.data.device != device or not into.data.is_contiguous() or into.data.numel() < _lib.kmer_words(16):
+            raise ValueError("into holds int64 words on the device of the columns")
+        capacity = into.capacity
+    if capacity is not None:
+        _check_kmer_capacity(capacity)
+    if (begin is None) != (end is None):
+        raise ValueError("begin and end go together")
+    if begin is not None:
+        begin = begin.to(torch.int64).contiguous(); end = end.to(torch.int64).contiguous()
+    if keep is not None:
+        keep = keep.to(torch.uint8).contiguous()
+    for t in (begin, end, keep):
+        if t is not None and (t.numel() != R or t.device != device):
+            raise ValueError("begin, end and keep have one entry per record, on the device of the columns")
+    cin, held = _columns_in(cols, titles=False)
+    adr = lambda t: None if t is None or not t.numel() else t.data_ptr()
+    new_table = lambda M: KmerTable(torch.empty(_lib.kmer_words(M), dtype=torch.int64, device=device), k, canonical)
+    sizing = into is None and capacity is None
+    table = into if into is not None else new_table(16 if sizing else capacity)
+    _quiesce(device)
+
+    def call():
+        return handle.columns_kmer_count(cin, adr(begin), adr(end), adr(keep), _lib.KmerRules(k, int(canonical), 1 if into is not None else 0, 0, table.capacity),
+                                         table.data.data_ptr())
+    try:
+        stats = call()
+    except _lib.DsrcGpuError as e:
+        if e.code != _lib.E_CAPACITY or not (sizing or into is not None):
+            raise
+        if into is not None:
+            into.data = into.grown(handle, e.need).data
+        else:
+            table = new_table(e.need)
+        stats = call()
+    del held
+    stats = dict(zip(_lib.KMER_STATS, stats))
+    if stats["overflow"]:
+        raise RuntimeError("k-mer count: %d occurrences lost to overflow" % stats["overflow"])
+    return table, stats

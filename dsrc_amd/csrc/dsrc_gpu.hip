@@ -52,6 +52,7 @@
 #include "k_columns_merge.h"
 #include "k_columns_dedup.h"
 #include "k_columns_profile.h"
+#include "k_columns_kmer.h"
 
 namespace
 {
@@ -2668,6 +2669,210 @@ int dsrcgpu_columns_profile(dsrcgpu_handle* h, const dsrcgpu_columns_in* in, con
 	HIPCHK(hipStreamSynchronize(s));
 	if (res[0] != COLE_NONE) return sel_input_error(h, res[0]);
 	for (u32 k = 0; k < PROF_N_TOTALS; ++k) totals[k] = res[k + 1];
+	return DSRCGPU_OK;
+}
+
+// ---- k-mer count (k_columns_kmer.h) --------------------------------------------------------------------------------------------------
+} // extern "C"
+namespace
+{
+// the 64-byte header of a caller's table, brought home and checked: the magic, k, canonical, M.  -> t (the table behind it), k, canonical
+int kmer_table_home(dsrcgpu_handle* h, const uint64_t* d_table, const char* what, u64 hdr[8], KmerTab& t, u32& k, u32& canonical)
+{
+	HIPCHK(hipMemcpyAsync(hdr, d_table, 8 * sizeof(u64), hipMemcpyDeviceToHost, h->stream));
+	HIPCHK(hipStreamSynchronize(h->stream));
+	k = (u32)((hdr[0] >> 8) & 255u); canonical = (u32)(hdr[0] & 255u);
+	const u32 bits = (u32)((hdr[0] >> 16) & 255u);
+	const u64 M = hdr[1];
+	if (hdr[0] >> 32 != KMER_MAGIC || k < 1 || k > DSRCGPU_KMER_MAX_K || canonical > 1 || bits > 63 || hdr[0] != kmer_header_word(k, canonical, bits) || M < 16 ||
+	    M > (1ull << 40) || (M & (M - 1)))
+		return fail(h, DSRCGPU_E_ARG, "%s: not a k-mer table (header word %016llx, capacity %llu)", what, (unsigned long long)hdr[0], (unsigned long long)M);
+	u64* const keys = const_cast<u64*>(d_table) + KMER_HEADER;
+	t = KmerTab{keys, keys + M, M - 1, bits == 0 ? ~0ull : (1ull << bits) - 1ull, (u32)std::min<u64>(M, KMER_PROBE_LIMIT)};
+	return DSRCGPU_OK;
+}
+
+u64 kmer_need(u64 keys)
+{
+	u64 need = 16;
+	while (need < 2 * keys) need <<= 1;
+	return need;
+}
+
+int kmer_queue_idle(dsrcgpu_handle* h)
+{
+	std::lock_guard<std::mutex> g(h->q_m);
+	if (h->q_started && h->q_pending) return fail(h, DSRCGPU_E_STATE, "batches of the queue form are still in flight on this handle");
+	return DSRCGPU_OK;
+}
+} // namespace
+extern "C" {
+
+// the k-mer count: the header comes home first under accumulate, then the check pass of the adapter plan and the window count; the
+// error word and W come home BEFORE the first launch that writes the table, so that every refusal leaves it untouched
+int dsrcgpu_columns_kmer_count(dsrcgpu_handle* h, const dsrcgpu_columns_in* in, const uint64_t* d_begin, const uint64_t* d_end, const uint8_t* d_keep,
+							   const dsrcgpu_kmer_rules* rules, uint64_t* d_table, uint64_t stats[16], uint64_t need[1])
+{
+	if (!h) return DSRCGPU_E_ARG;
+	if (!rules || !stats || !need || !d_table) return fail(h, DSRCGPU_E_ARG, "null argument");
+	for (u32 i = 0; i < KMER_N_STATS; ++i) stats[i] = 0;
+	need[0] = 0;
+	ColIn c;
+	{ const int rc = sel_in_args(h, in, false, c, false); if (rc) return rc; }
+	const u32 k = rules->k, bits = rules->hash_bits;
+	const u64 M = rules->capacity;
+	if (k < 1 || k > DSRCGPU_KMER_MAX_K) return fail(h, DSRCGPU_E_ARG, "kmer rules: k must be 1 .. %u", (u32)DSRCGPU_KMER_MAX_K);
+	if (rules->canonical > 1) return fail(h, DSRCGPU_E_ARG, "kmer rules: canonical must be 0 or 1");
+	if (rules->accumulate > 1) return fail(h, DSRCGPU_E_ARG, "kmer rules: accumulate must be 0 or 1");
+	if (bits > 64) return fail(h, DSRCGPU_E_ARG, "kmer rules: hash_bits above 64");
+	if (M < 16 || M > (1ull << 40) || (M & (M - 1))) return fail(h, DSRCGPU_E_ARG, "kmer rules: capacity must be a power of two, 16 .. 2^40");
+	if (rules->reserved[0] | rules->reserved[1] | rules->reserved[2] | rules->reserved[3]) return fail(h, DSRCGPU_E_ARG, "kmer rules: reserved fields must be 0");
+	if (!d_begin != !d_end) return fail(h, DSRCGPU_E_ARG, "columns: d_begin and d_end go together");
+	HIPCHK(hipSetDevice(h->device));
+	hipStream_t s = h->stream;
+	u64 hdr[8] = {kmer_header_word(k, rules->canonical, bits), M, 0, 0, 0, 0, 0, 0};
+	u64* const keys = d_table + KMER_HEADER;
+	KmerTab t{keys, keys + M, M - 1, bits == 0 || bits == 64 ? ~0ull : (1ull << bits) - 1ull, (u32)std::min<u64>(M, KMER_PROBE_LIMIT)};
+	if (rules->accumulate)
+	{
+		u64 have[8]; KmerTab th; u32 hk, hc;
+		{ const int rc = kmer_table_home(h, d_table, "kmer count, accumulate", have, th, hk, hc); if (rc) return rc; }
+		if (have[0] != hdr[0] || have[1] != M)
+			return fail(h, DSRCGPU_E_ARG, "kmer count, accumulate: the table holds k = %u, canonical = %u, capacity %llu; the rules ask for %u, %u, %llu (or another hash_bits)",
+			            hk, hc, (unsigned long long)have[1], k, rules->canonical, (unsigned long long)M);
+		for (u32 i = 0; i < 8; ++i) hdr[i] = have[i];
+	}
+	const auto init = [&]() -> int {
+		HIPCHK(hipMemsetAsync(t.keys, 0xFF, (size_t)M * 8, s));
+		HIPCHK(hipMemsetAsync(t.counts, 0, (size_t)M * 8, s));
+		HIPCHK(hipMemcpyAsync(d_table, hdr, sizeof(hdr), hipMemcpyHostToDevice, s));
+		return DSRCGPU_OK;
+	};
+	if (c.n_recs == 0)
+	{
+		if (!rules->accumulate) { const int rc = init(); if (rc) return rc; HIPCHK(hipStreamSynchronize(s)); }
+		stats[KMER_DISTINCT_AFTER] = hdr[2]; stats[KMER_TOTAL_AFTER] = hdr[3];
+		return DSRCGPU_OK;
+	}
+	{ const int rc = ensure_arena(h, (1 + KMER_N_STATS) * 8 + 1024); if (rc) return rc; }
+	const size_t o_res = h->arena.alloc((1 + KMER_N_STATS) * 8);
+	if (h->arena.failed) return fail(h, DSRCGPU_E_NOMEM, "arena exhausted (kmer count)");
+	u64* d_res = AP<u64>(h, o_res);                      // the error word, the sixteen statistics
+	HIPCHK(hipMemsetAsync(d_res, 0xFF, 8, s));
+	HIPCHK(hipMemsetAsync(d_res + 1, 0, KMER_N_STATS * 8, s));
+	const AdaptPlanIn w{d_begin, d_end, d_keep};
+	const u64 wpg = WG / 64;
+	const dim3 g_check((u32)std::max<u64>(1, std::min<u64>(1024, (c.n_recs + WG - 1) / WG)));
+	hipLaunchKernelGGL(k_adapt_check, g_check, dim3(WG), 0, s, c, w, d_res); KCHK();
+	hipLaunchKernelGGL(k_kmer_windows, g_check, dim3(WG), 0, s, c, w, k, d_res + 1, d_res); KCHK();
+	u64 res[1 + KMER_N_STATS];
+	HIPCHK(hipMemcpyAsync(res, d_res, sizeof(res), hipMemcpyDeviceToHost, s));
+	HIPCHK(hipStreamSynchronize(s));
+	if (res[0] != COLE_NONE) return sel_input_error(h, res[0]);
+	const u64 W = res[1 + KMER_WINDOWS];
+	if (hdr[2] + W > M / 4 * 3)
+	{
+		need[0] = kmer_need(hdr[2] + W);
+		return fail(h, DSRCGPU_E_CAPACITY, "kmer count: %llu keys in the table and %llu windows in this call; a capacity of %llu holds %llu, %llu would do",
+		            (unsigned long long)hdr[2], (unsigned long long)W, (unsigned long long)M, (unsigned long long)(M / 4 * 3), (unsigned long long)need[0]);
+	}
+	if (!rules->accumulate) { const int rc = init(); if (rc) return rc; }
+	const dim3 g_count((u32)std::max<u64>(1, std::min<u64>(4096, (c.n_recs + wpg - 1) / wpg)));
+	const long variant = hook_int("DSRC_GPU_KMER_VARIANT", 0);       // test hook: 1 = no run aggregation, 2 = no plain load in front of the CAS
+	if (variant == 1) { hipLaunchKernelGGL((k_kmer_count<false, true>), g_count, dim3(WG), 0, s, c, w, k, rules->canonical, t, d_res + 1, d_res); KCHK(); }
+	else if (variant == 2) { hipLaunchKernelGGL((k_kmer_count<true, false>), g_count, dim3(WG), 0, s, c, w, k, rules->canonical, t, d_res + 1, d_res); KCHK(); }
+	else { hipLaunchKernelGGL((k_kmer_count<true, true>), g_count, dim3(WG), 0, s, c, w, k, rules->canonical, t, d_res + 1, d_res); KCHK(); }
+	hipLaunchKernelGGL(k_kmer_header, dim3(1), dim3(64), 0, s, d_table, d_res + 1 + KMER_NEW, d_res + 1 + KMER_COUNTED, d_res + 1 + KMER_OVERFLOW, 0ull,
+	                   d_res + 1 + KMER_DISTINCT_AFTER, d_res + 1 + KMER_TOTAL_AFTER, d_res); KCHK();
+	HIPCHK(hipMemcpyAsync(res, d_res, sizeof(res), hipMemcpyDeviceToHost, s));
+	HIPCHK(hipStreamSynchronize(s));
+	for (u32 i = 0; i < KMER_N_STATS; ++i) stats[i] = res[1 + i];
+	return DSRCGPU_OK;
+}
+
+// both headers come home and are checked, the 3/4 rule is applied to what the destination may hold afterwards, then the merge
+int dsrcgpu_kmer_table_merge(dsrcgpu_handle* h, const uint64_t* d_src, uint64_t* d_dst, uint64_t stats[8], uint64_t need[1])
+{
+	if (!h) return DSRCGPU_E_ARG;
+	if (!d_src || !d_dst || !stats || !need) return fail(h, DSRCGPU_E_ARG, "null argument");
+	for (u32 i = 0; i < KMERGE_N_STATS; ++i) stats[i] = 0;
+	need[0] = 0;
+	if (d_src == d_dst) return fail(h, DSRCGPU_E_ARG, "kmer merge: a table cannot be merged into itself");
+	{ const int rc = kmer_queue_idle(h); if (rc) return rc; }
+	HIPCHK(hipSetDevice(h->device));
+	hipStream_t s = h->stream;
+	u64 hs[8], hd[8]; KmerTab ts, td; u32 ks, cs, kd, cd;
+	{ const int rc = kmer_table_home(h, d_src, "kmer merge, source", hs, ts, ks, cs); if (rc) return rc; }
+	{ const int rc = kmer_table_home(h, d_dst, "kmer merge, destination", hd, td, kd, cd); if (rc) return rc; }
+	if (ks != kd || cs != cd) return fail(h, DSRCGPU_E_ARG, "kmer merge: the source holds k = %u, canonical = %u, the destination %u, %u", ks, cs, kd, cd);
+	if (hd[2] + hs[2] > hd[1] / 4 * 3)
+	{
+		need[0] = kmer_need(hd[2] + hs[2]);
+		return fail(h, DSRCGPU_E_CAPACITY, "kmer merge: %llu keys in the destination and %llu in the source; a capacity of %llu holds %llu, %llu would do",
+		            (unsigned long long)hd[2], (unsigned long long)hs[2], (unsigned long long)hd[1], (unsigned long long)(hd[1] / 4 * 3), (unsigned long long)need[0]);
+	}
+	{ const int rc = ensure_arena(h, KMERGE_N_STATS * 8 + 1024); if (rc) return rc; }
+	const size_t o_res = h->arena.alloc(KMERGE_N_STATS * 8);
+	if (h->arena.failed) return fail(h, DSRCGPU_E_NOMEM, "arena exhausted (kmer merge)");
+	u64* d_res = AP<u64>(h, o_res);
+	HIPCHK(hipMemsetAsync(d_res, 0, KMERGE_N_STATS * 8, s));
+	const u64 slots = hs[1];
+	hipLaunchKernelGGL(k_kmer_merge, dim3((u32)std::max<u64>(1, std::min<u64>(4096, (slots + WG - 1) / WG))), dim3(WG), 0, s, ts.keys, ts.counts, slots, td, d_res); KCHK();
+	hipLaunchKernelGGL(k_kmer_header, dim3(1), dim3(64), 0, s, d_dst, d_res + KMERGE_NEW, d_res + KMERGE_ADDED, d_res + KMERGE_OVERFLOW, hs[4],
+	                   d_res + KMERGE_DISTINCT_AFTER, d_res + KMERGE_TOTAL_AFTER, (const u64*)nullptr); KCHK();
+	u64 res[KMERGE_N_STATS];
+	HIPCHK(hipMemcpyAsync(res, d_res, sizeof(res), hipMemcpyDeviceToHost, s));
+	HIPCHK(hipStreamSynchronize(s));
+	for (u32 i = 0; i < KMERGE_N_STATS; ++i) stats[i] = res[i];
+	return DSRCGPU_OK;
+}
+
+int dsrcgpu_kmer_spectrum(dsrcgpu_handle* h, const uint64_t* d_table, uint32_t n_bins, uint64_t* d_hist, uint64_t totals[4])
+{
+	if (!h) return DSRCGPU_E_ARG;
+	if (!d_table || !d_hist || !totals) return fail(h, DSRCGPU_E_ARG, "null argument");
+	for (u32 i = 0; i < KSPEC_N_TOTALS; ++i) totals[i] = 0;
+	if (n_bins < 2 || n_bins > DSRCGPU_KMER_MAX_BINS) return fail(h, DSRCGPU_E_ARG, "kmer spectrum: n_bins must be 2 .. %u", (u32)DSRCGPU_KMER_MAX_BINS);
+	{ const int rc = kmer_queue_idle(h); if (rc) return rc; }
+	HIPCHK(hipSetDevice(h->device));
+	hipStream_t s = h->stream;
+	u64 hdr[8]; KmerTab t; u32 k, canonical;
+	{ const int rc = kmer_table_home(h, d_table, "kmer spectrum", hdr, t, k, canonical); if (rc) return rc; }
+	{ const int rc = ensure_arena(h, KSPEC_N_TOTALS * 8 + 1024); if (rc) return rc; }
+	const size_t o_res = h->arena.alloc(KSPEC_N_TOTALS * 8);
+	if (h->arena.failed) return fail(h, DSRCGPU_E_NOMEM, "arena exhausted (kmer spectrum)");
+	u64* d_res = AP<u64>(h, o_res);
+	HIPCHK(hipMemsetAsync(d_res, 0, KSPEC_N_TOTALS * 8, s));
+	HIPCHK(hipMemsetAsync(d_hist, 0, (size_t)n_bins * 8, s));
+	const u64 slots = hdr[1];
+	// (every workgroup ends with a flush of its LDS bins: no more workgroups than the chip holds at a time)
+	hipLaunchKernelGGL(k_kmer_spectrum, dim3((u32)std::max<u64>(1, std::min<u64>(512, (slots + WG - 1) / WG))), dim3(WG), 0, s, t.keys, t.counts, slots, n_bins, d_hist, d_res); KCHK();
+	HIPCHK(hipMemcpyAsync(totals, d_res, KSPEC_N_TOTALS * 8, hipMemcpyDeviceToHost, s));
+	HIPCHK(hipStreamSynchronize(s));
+	return DSRCGPU_OK;
+}
+
+int dsrcgpu_kmer_lookup(dsrcgpu_handle* h, const uint64_t* d_table, const uint64_t* d_kmers, uint64_t n, uint64_t* d_counts, uint64_t* invalid)
+{
+	if (!h) return DSRCGPU_E_ARG;
+	if (!d_table || !invalid) return fail(h, DSRCGPU_E_ARG, "null argument");
+	*invalid = 0;
+	if (n >> 56) return fail(h, DSRCGPU_E_ARG, "kmer lookup: 2^56 queries and more");
+	if (n && (!d_kmers || !d_counts)) return fail(h, DSRCGPU_E_ARG, "null argument");
+	{ const int rc = kmer_queue_idle(h); if (rc) return rc; }
+	HIPCHK(hipSetDevice(h->device));
+	hipStream_t s = h->stream;
+	u64 hdr[8]; KmerTab t; u32 k, canonical;
+	{ const int rc = kmer_table_home(h, d_table, "kmer lookup", hdr, t, k, canonical); if (rc) return rc; }
+	if (n == 0) return DSRCGPU_OK;
+	{ const int rc = ensure_arena(h, 8 + 1024); if (rc) return rc; }
+	const size_t o_res = h->arena.alloc(8);
+	if (h->arena.failed) return fail(h, DSRCGPU_E_NOMEM, "arena exhausted (kmer lookup)");
+	u64* d_res = AP<u64>(h, o_res);
+	HIPCHK(hipMemsetAsync(d_res, 0, 8, s));
+	hipLaunchKernelGGL(k_kmer_lookup, dim3((u32)std::max<u64>(1, std::min<u64>(4096, (n + WG - 1) / WG))), dim3(WG), 0, s, t, k, canonical, d_kmers, n, d_counts, d_res); KCHK();
+	HIPCHK(hipMemcpyAsync(invalid, d_res, 8, hipMemcpyDeviceToHost, s));
+	HIPCHK(hipStreamSynchronize(s));
 	return DSRCGPU_OK;
 }
 

@@ -531,8 +531,9 @@ int dsrcgpu_columns_merge_device(dsrcgpu_handle* h, const dsrcgpu_columns_in* in
  * file give what one call on all of it gives.  totals (host) is this call's own tot[8] either way.  Everything is an integer sum: the
  * result does not depend on the order in which the device takes the records and is bit-reproducible; no counter wraps below 2^64.
  * n_records == 0: DSRCGPU_OK, totals 0, d_profile zeroed if accumulate == 0 and untouched otherwise.
- * Not done here: k-mer counts, a duplication estimate (dsrcgpu_columns_dedup_plan has the duplication levels), over-represented
- * sequences, per-tile quality (nothing here reads the titles),
+ * Not done here: k-mer counts and over-represented k-mers (dsrcgpu_columns_kmer_count below takes the same plan), a duplication
+ * estimate (dsrcgpu_columns_dedup_plan has the duplication levels), over-represented
+ * whole sequences, per-tile quality (nothing here reads the titles),
  * a per-cycle quality HISTOGRAM (per cycle there is the sum and the count, so the mean, not the quartiles).
  * On any error d_profile is untouched.  DSRCGPU_E_ARG: n_cycles 0 or above DSRCGPU_PROFILE_MAX_CYCLES; accumulate above 1; a non-zero
  * reserved field; a half-given range pair; a null d_profile, rules or totals; a null in->d_quals (or d_bases) with bases_len > 0.
@@ -553,6 +554,99 @@ int dsrcgpu_columns_profile(dsrcgpu_handle* h, const dsrcgpu_columns_in* in,
 		const dsrcgpu_profile_rules* rules,
 		uint64_t* d_profile   /* device, DSRCGPU_PROFILE_WORDS(n_cycles) words */,
 		uint64_t totals[8]    /* host: this call's own contribution, whatever accumulate is */);
+
+/* dsrcgpu_columns_kmer_count: the canonical k-mer table of the records of `in` under a plan -- what the k-mer spectrum (genome size,
+ * error rate), over-represented k-mers and contaminant screens are read from.  Conventions as dsrcgpu_columns_profile: the handle's
+ * own lane and stream, a few words of scratch from the arena, synchronised before it returns, codec state left alone, a colour-space
+ * handle: DSRCGPU_E_ARG.  Of `in`, d_bases and d_seq_offs are read; everything else may be NULL.  The plan, as the planners give it:
+ * d_begin / d_end (both NULL = whole reads, one without the other: DSRCGPU_E_ARG) and d_keep (NULL = every record; any non-zero byte
+ * considers the record).
+ * Packing.  Base codes are those of dsrcgpu_columns_in: A C G T = 0 1 2 3; every other code (N, IUPAC, U = 16, 255) is NOT a base.  A
+ * k-mer, k in 1 .. DSRCGPU_KMER_MAX_K, is the 2k-bit integer of k consecutive bases of a record's RANGE, first base most significant.
+ * Its reverse complement reverses the order and takes 3 - code of each base.  canonical = 1: the key is the numeric minimum of the
+ * two; canonical = 0: the forward value.  k <= 31 leaves the all-ones word free as the EMPTY mark.
+ *   for r = 0 .. n_records - 1:
+ *     if d_keep and d_keep[r] == 0: stats[1] += 1, next r
+ *     stats[0] += 1; b = d_begin[r]; e = d_end[r]
+ *     if e - b < k: stats[2] += 1, next r
+ *     for p = b .. e - k:                                           (e - b - k + 1 windows)
+ *       stats[3] += 1
+ *       if any of d_bases[p .. p + k) is above 3: stats[5] += 1     (a BROKEN window adds nothing)
+ *       else: key = canonical ? min(fwd, rc) : fwd; count[key] += 1
+ * Records of the second mate are a second call with accumulate = 1; there is no pair rule.
+ * The table is ONE caller-owned array of DSRCGPU_KMER_WORDS(M) = 8 + 2 M uint64 words in HBM, M = rules->capacity a power of two in
+ * 16 .. 2^40:
+ *   [0] 0x4B4D4552 << 32 | (hash_bits mod 64) << 16 | k << 8 | canonical   [1] M   [2] distinct keys   [3] occurrences counted
+ *   [4] occurrences lost to overflow over the table's life   [5 .. 7] 0
+ *   8       keys[M]     EMPTY = all ones
+ *   8 + M   counts[M]
+ * Slot order is unspecified: it depends on the order in which the device takes the windows.  The header and the SET of (key, count)
+ * pairs do not, and they are what two runs, or a run and the loop above, agree on bit for bit.  The header is kept up to date on the
+ * device by the library's kernels; a caller reads it and never writes it.
+ * accumulate == 0: the table is initialised (empty) first; 1: the header must match k, canonical, hash_bits and capacity, else
+ * DSRCGPU_E_ARG with nothing touched, and this call's counts are added.
+ * The 3/4 rule: with W = stats[3], the windows of the call (summed by the check pass, before the table is written), a call with
+ * distinct_before + W > 3 M / 4 returns DSRCGPU_E_CAPACITY with the table untouched and need[0] = the smallest power of two >= 2 *
+ * (distinct_before + W), and at least 16.  So the load is at or under 3/4 at every moment of every call.
+ * A probe walks at most min(M, DSRCGPU_KMER_PROBE_LIMIT) slots; an occurrence that meets neither its key nor an empty slot in that
+ * walk is counted in overflow and dropped.  With the full hash and a load of 3/4 this does not happen; hash_bits can force it.
+ * PRESENT MEANS EXACT: slots are never freed, so a key is either in the table with its exact count, or wholly absent with all its
+ * occurrences in overflow.  overflow > 0 is no error code: it is a statistic, and header word 4 accumulates it.
+ * stats (host), all independent of the order: [0] records considered, [1] records that came in dropped, [2] considered records
+ * without a window, [3] windows, [4] k-mers counted, [5] broken windows, [6] keys new to the table, [7] overflow, [8] distinct keys
+ * after the call, [9] occurrences in the table after the call, [10 .. 15] 0.  [3] == [4] + [5] + [7].
+ * n_records == 0: DSRCGPU_OK; the table is initialised under accumulate = 0 and only checked under 1.
+ * Not done here: k above 31, minimizers, per-read annotations (median abundance, digital normalisation, contaminant keep flags: a
+ * fifth planner can sit on dsrcgpu_kmer_lookup), approximate counting (Bloom filters, count-min), tables that span several GPUs
+ * (dsrcgpu_kmer_table_merge sums the tables of ranks), anything that reorders records.
+ * On any error the table is untouched.  DSRCGPU_E_ARG: k 0 or above 31; canonical or accumulate above 1; hash_bits above 64; a
+ * capacity that is no power of two in 16 .. 2^40; a non-zero reserved field; a half-given range pair; a null d_table, rules, stats
+ * or need; under accumulate a header that is no table's or does not match the rules.  DSRCGPU_E_INPUT exactly as
+ * dsrcgpu_columns_profile.  No input makes a kernel read outside the caller's arrays or write outside the DSRCGPU_KMER_WORDS(M) words
+ * of d_table, which must not overlap the inputs. */
+#define DSRCGPU_KMER_MAX_K 31
+#define DSRCGPU_KMER_PROBE_LIMIT 1024
+#define DSRCGPU_KMER_MAX_BINS 65536
+#define DSRCGPU_KMER_WORDS(M) (8ull + 2ull * (M))        /* uint64 words of a table of M slots */
+typedef struct dsrcgpu_kmer_rules
+{
+	uint32_t k;             /* 1 .. DSRCGPU_KMER_MAX_K */
+	uint32_t canonical;     /* 1: a k-mer and its reverse complement are one key (the lower word); 0: the forward word */
+	uint32_t accumulate;    /* 0: the table is initialised first; 1: this call's counts are ADDED to the table d_table holds */
+	uint32_t hash_bits;     /* a diagnostic, as in dsrcgpu_dedup_rules: 0 or 64 = the full hash, 1 .. 63 = that many low bits.  It is part
+	                           of the table's header (lookups must walk as the inserts did); no (key, count) pair depends on it unless
+	                           it forces overflow */
+	uint64_t capacity;      /* M: slots of the table, a power of two in 16 .. 2^40 */
+	uint32_t reserved[4];   /* must be 0 */
+} dsrcgpu_kmer_rules;
+
+int dsrcgpu_columns_kmer_count(dsrcgpu_handle* h, const dsrcgpu_columns_in* in,
+		const uint64_t* d_begin, const uint64_t* d_end, const uint8_t* d_keep   /* device, may be NULL: the plan, as the planners give it */,
+		const dsrcgpu_kmer_rules* rules,
+		uint64_t* d_table     /* device, DSRCGPU_KMER_WORDS(rules->capacity) words */,
+		uint64_t stats[16]    /* host */,
+		uint64_t need[1]      /* host: under DSRCGPU_E_CAPACITY the capacity that would do, else 0 */);
+
+/* Every (key, count) of the table d_src is added into the table d_dst; d_src is only read.  The two must hold the same k and
+ * canonical and may have any two capacities (and hash_bits): this grows a table (merge into an empty larger one), sums the tables of
+ * batches, and sums the tables of ranks.  The 3/4 rule with W = the distinct keys of d_src: distinct(dst) + distinct(src) > 3 M(dst) /
+ * 4: DSRCGPU_E_CAPACITY, d_dst untouched, need[0] as above.  Present means exact holds for d_dst as above; a key that cannot be
+ * placed adds its whole count to overflow.  d_dst's header word 4 also takes over what d_src had lost.
+ * stats (host): [0] keys of d_src, [1] of them new to d_dst, [2] occurrences added, [3] occurrences lost to overflow, [4] distinct
+ * keys of d_dst afterwards, [5] its occurrences afterwards, [6 .. 7] 0.
+ * DSRCGPU_E_ARG, nothing written: a null argument, d_src == d_dst, a header that is no table's, different k or canonical. */
+int dsrcgpu_kmer_table_merge(dsrcgpu_handle* h, const uint64_t* d_src, uint64_t* d_dst, uint64_t stats[8], uint64_t need[1]);
+
+/* The k-mer spectrum: d_hist[c] (device, n_bins uint64 words, overwritten) = the number of distinct keys counted c times; counts
+ * >= n_bins - 1 fold into the last bin, d_hist[0] = 0.  totals (host): [0] distinct keys, [1] occurrences, [2] keys counted once,
+ * [3] the largest count.  n_bins in 2 .. DSRCGPU_KMER_MAX_BINS, else DSRCGPU_E_ARG; a header that is no table's: DSRCGPU_E_ARG;
+ * d_hist is untouched on any error. */
+int dsrcgpu_kmer_spectrum(dsrcgpu_handle* h, const uint64_t* d_table, uint32_t n_bins, uint64_t* d_hist, uint64_t totals[4]);
+
+/* d_counts[i] (device, n uint64 words) = the count of the packed k-mer d_kmers[i] (first base most significant), 0 for a key that
+ * is not in the table.  Under a canonical table a query is canonicalised first: a k-mer and its reverse complement give the same
+ * answer.  A word >= 4^k gets 0 and is counted in *invalid (host).  The walk is the insert's, without a write. */
+int dsrcgpu_kmer_lookup(dsrcgpu_handle* h, const uint64_t* d_table, const uint64_t* d_kmers, uint64_t n, uint64_t* d_counts, uint64_t* invalid);
 
 /* Queue form of DsrcCompressor::Process (src/DsrcWorker.cpp:39-70):
  *   fastqQueue.Pop(partId, chunk)            -> dsrcgpu_submit(partId, chunk)      (bytes are copied into page-locked staging)
