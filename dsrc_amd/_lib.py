@@ -29,6 +29,7 @@ EXPORTS = [
     "dsrcgpu_columns_trim_plan", "dsrcgpu_columns_select_device", "dsrcgpu_columns_adapter_plan", "dsrcgpu_columns_pair_plan",
     "dsrcgpu_columns_profile", "dsrcgpu_columns_merge_device", "dsrcgpu_columns_dedup_plan",
     "dsrcgpu_columns_kmer_count", "dsrcgpu_kmer_table_merge", "dsrcgpu_kmer_spectrum", "dsrcgpu_kmer_lookup",
+    "dsrcgpu_columns_kmer_plan",
 ]
 
 # error codes of include/dsrc_gpu.h that callers tell apart (DsrcGpuError.code)
@@ -197,6 +198,33 @@ KMER_SPECTRUM_TOTALS = ("distinct", "occurrences", "singletons", "largest_count"
 def kmer_words(capacity: int) -> int:
     """DSRCGPU_KMER_WORDS: the uint64 words of a k-mer table of `capacity` slots."""
     return 8 + 2 * capacity
+
+
+class KmerPlanRules(C.Structure):
+    """dsrcgpu_kmer_plan_rules: KmerPlanRules(min_count, min_hits, max_hits, min_hit_permille, max_hit_permille, min_median, max_median,
+    trim, min_length, want_median); max_hits / max_median None = no upper limit.  The library is the one that refuses figures out of
+    range."""
+    _fields_ = [("min_count", C.c_uint64), ("min_hits", C.c_uint32), ("max_hits", C.c_uint32), ("min_hit_permille", C.c_uint32),
+                ("max_hit_permille", C.c_uint32), ("min_median", C.c_uint32), ("max_median", C.c_uint32), ("trim", C.c_uint32),
+                ("min_length", C.c_uint32), ("want_median", C.c_uint32), ("reserved", C.c_uint32 * 4)]
+
+    def __init__(self, min_count=1, min_hits=0, max_hits=None, min_hit_permille=0, max_hit_permille=1000, min_median=0, max_median=None, trim=0,
+                 min_length=1, want_median=0, reserved=(0, 0, 0, 0)):
+        super().__init__()
+        self.min_count, self.min_hits, self.max_hits = min_count, min_hits, KMER_PLAN_NO_LIMIT if max_hits is None else max_hits
+        self.min_hit_permille, self.max_hit_permille = min_hit_permille, max_hit_permille
+        self.min_median, self.max_median = min_median, KMER_PLAN_NO_LIMIT if max_median is None else max_median
+        self.trim, self.min_length, self.want_median = trim, min_length, want_median
+        self.reserved = (C.c_uint32 * 4)(*reserved)
+
+
+KMER_PLAN_NO_LIMIT = 0xFFFFFFFF  # max_hits / max_median: no upper limit
+KMER_PLAN_COUNT_CAP = 65535      # DSRCGPU_KMER_PLAN_COUNT_CAP: the median is that of the counts capped here
+KMER_PLAN_LDS_WINDOWS = 1024     # DSRCGPU_KMER_PLAN_LDS_WINDOWS: longer ranges keep their counts in HBM scratch under want_median
+KMER_PLAN_TRIM = {"none": 0, "first_miss": 1, "first_hit": 2}
+KMER_PLAN_STATS = ("records_considered", "records_came_dropped", "records_no_window", "windows", "windows_good", "hits", "records_kept",
+                   "records_with_hit", "records_trimmed", "bases_cut", "dropped_hits", "dropped_hit_share", "dropped_median", "dropped_length",
+                   "bases_kept")
 
 
 class HostColumns(typing.NamedTuple):
@@ -633,6 +661,19 @@ class Handle:
         invalid = C.c_uint64()
         self._chk(self.L.dsrcgpu_kmer_lookup(self.h, C.c_void_p(d_table), C.c_void_p(d_kmers), C.c_uint64(n), C.c_void_p(d_counts), C.byref(invalid)))
         return invalid.value
+
+    def columns_kmer_plan(self, cols_in: ColumnsIn, rules: KmerPlanRules, d_table, d_begin_in, d_end_in, d_keep_in, d_begin, d_end, d_keep,
+                          d_good=None, d_hits=None, d_median=None):
+        """dsrcgpu_columns_kmer_plan: every window of the records of `cols_in` under the plan d_begin_in / d_end_in / d_keep_in (device
+        addresses or None: whole reads, every record) looked up in the table d_table (of columns_kmer_count; only read) -> the
+        narrowed plan in d_begin / d_end (uint64 each), d_keep (uint8) and, if wanted, the good windows, the hits and the median count
+        of every record in d_good / d_hits / d_median (uint64 each), all device memory of n_records entries; an output may be the very
+        array of its input.  Returns the sixteen statistics (KMER_PLAN_STATS names the first fifteen)."""
+        stats = (C.c_uint64 * 16)()
+        self._chk(self.L.dsrcgpu_columns_kmer_plan(self.h, C.byref(cols_in), C.byref(rules), C.c_void_p(d_table), C.c_void_p(d_begin_in),
+                                                   C.c_void_p(d_end_in), C.c_void_p(d_keep_in), C.c_void_p(d_begin), C.c_void_p(d_end),
+                                                   C.c_void_p(d_keep), C.c_void_p(d_good), C.c_void_p(d_hits), C.c_void_p(d_median), stats))
+        return list(stats)
 
     def columns_select_device(self, cols_in: ColumnsIn, d_begin, d_end, d_keep, out: Columns, d_source=None):
         """dsrcgpu_columns_select_device: the kept records of `cols_in`, cut to [begin, end), compacted into the device arrays `out`

@@ -1,7 +1,8 @@
 """Records as torch tensors: decode_columns (dsrcgpu_decompress_batch_columns_device), the way back, encode_columns
 (dsrcgpu_compress_columns_device), and what runs between the two: trim_plan (dsrcgpu_columns_trim_plan), adapter_plan
-(dsrcgpu_columns_adapter_plan), pair_plan (dsrcgpu_columns_pair_plan), dedup_plan (dsrcgpu_columns_dedup_plan), merge_pairs
-(dsrcgpu_columns_merge_device), select_columns (dsrcgpu_columns_select_device), filter_columns and, for paired-end data,
+(dsrcgpu_columns_adapter_plan), kmer_plan (dsrcgpu_columns_kmer_plan, with columns_from_sequences for its reference), pair_plan
+(dsrcgpu_columns_pair_plan), dedup_plan (dsrcgpu_columns_dedup_plan), merge_pairs (dsrcgpu_columns_merge_device), select_columns
+(dsrcgpu_columns_select_device), filter_columns and, for paired-end data,
 filter_pairs, the report on either side of them, profile_columns (dsrcgpu_columns_profile), and the k-mer table of a plan, count_kmers
 and KmerTable (dsrcgpu_columns_kmer_count, dsrcgpu_kmer_table_merge, dsrcgpu_kmer_spectrum, dsrcgpu_kmer_lookup), include/dsrc_gpu.h.
 
@@ -340,7 +341,7 @@ def profile_columns(handle: _lib.Handle, cols: RecordColumns, begin=None, end=No
 
 def filter_columns(handle: _lib.Handle, cols: RecordColumns, titles: bool = True, adapters=None, adapter_min_overlap: int = 3,
                    adapter_max_error_permille: int = 100, profile: bool = False, dedup: bool = False, dedup_key_bases: int = 0,
-                   dedup_prefer: str = "first", kmers=None, **rules):
+                   dedup_prefer: str = "first", kmers=None, screen=None, **rules):
     """trim_plan(**rules) and select_columns with its plan in sequence: -> (RecordColumns of the trimmed, kept records, stats).
     adapters (see adapter_plan): between the two, adapter_plan narrows the trim plan -- the quality trim first, the adapter second,
     the order of cutadapt and fastp -- with the same min_length; stats is then the trim plan's dict plus a key "adapter" that holds
@@ -352,9 +353,14 @@ def filter_columns(handle: _lib.Handle, cols: RecordColumns, titles: bool = True
     record of every set of exact duplicates; stats gets "dedup", its dict, the number of records that come out is
     stats["dedup"]["records_kept"], and "profile_after" reflects it.
     kmers=k (an int, 1 .. 31): stats gets "kmers_after", the KmerTable of count_kmers(k) under the final plan on `cols` -- the
-    canonical k-mers of the records that come out, and it needs no select."""
+    canonical k-mers of the records that come out, and it needs no select.
+    screen (a dict of kmer_plan keywords, its `table` among them): behind the adapter plan and in front of dedup, kmer_plan narrows the
+    plan against that table -- a contaminant screen (max_hits=0) or an abundance trim -- with the filter's min_length unless the dict
+    gives one; stats gets "screen", its dict, and profile, kmers and the select see the narrowed plan."""
     if adapters is not None:
         codes = _adapter_codes(adapters)
+    if screen is not None:
+        _check_screen(screen, cols)
     if kmers is not None:
         _check_int("kmers", kmers, 1, _lib.KMER_MAX_K)
     if dedup:
@@ -364,6 +370,10 @@ def filter_columns(handle: _lib.Handle, cols: RecordColumns, titles: bool = True
         begin, end, keep, a_stats = adapter_plan(handle, cols, codes, begin, end, keep, adapter_min_overlap, adapter_max_error_permille,
                                                  rules.get("min_length", 1))
         stats = dict(stats, adapter=a_stats)
+    if screen is not None:
+        begin, end, keep, s_stats = kmer_plan(handle, cols, begin=begin, end=end, keep=keep,
+                                              **dict(dict(min_length=rules.get("min_length", 1)), **screen))
+        stats = dict(stats, screen=s_stats)
     if dedup:
         keep, d_stats = dedup_plan(handle, cols, begin=begin, end=end, keep=keep, key_bases=dedup_key_bases, prefer=dedup_prefer)
         stats = dict(stats, dedup=d_stats)
@@ -559,7 +569,8 @@ def merge_pairs(handle: _lib.Handle, cols1: RecordColumns, cols2: RecordColumns,
 def filter_pairs(handle: _lib.Handle, cols1: RecordColumns, cols2: RecordColumns, titles: bool = True, adapters1=None, adapters2=None,
                  overlap: bool = True, pair_min_overlap: int = 30, pair_max_mismatches: int = 5, pair_max_error_permille: int = 200,
                  adapter_min_overlap: int = 3, adapter_max_error_permille: int = 100, profile: bool = False, merge: bool = False,
-                 merge_quality_cap: int = 41, dedup: bool = False, dedup_key_bases: int = 0, dedup_prefer: str = "first", kmers=None, **rules):
+                 merge_quality_cap: int = 41, dedup: bool = False, dedup_key_bases: int = 0, dedup_prefer: str = "first", kmers=None, screen=None,
+                 **rules):
     """filter_columns for paired-end data: per side trim_plan(**rules) and, if adapters<s> is given, adapter_plan; then pair_plan with
     the same min_length, which cuts read-through found from the overlap of the mates and decides per PAIR; then one select_columns per
     side with that side's ranges and the joint keep -> (out1, out2, stats), out1.n_records == out2.n_records always and record j of
@@ -577,9 +588,15 @@ def filter_pairs(handle: _lib.Handle, cols1: RecordColumns, cols2: RecordColumns
     dict, the pairs that come out -- merged ones included -- number stats["dedup"]["records_kept"], and "profile_after" reflects it.
     kmers=k (an int, 1 .. 31): stats gets "kmers_after", ONE KmerTable with the canonical k-mers of both sides under the final
     ranges and the final keep -- count_kmers(k) on read 1, then on read 2 into the same table; of the mates out1 / out2, so under
-    merge=True without the merged reads."""
+    merge=True without the merged reads.
+    screen (a dict of kmer_plan keywords, its `table` among them): per side, behind that side's adapter plan and in front of the pair
+    plan, kmer_plan narrows the side's plan against that table, with the filter's min_length unless the dict gives one; the pair plan
+    (overlap=False: keep1 & keep2) then makes it a decision per PAIR -- a pair goes if either mate is screened out, as in BBDuk.
+    stats["read1"]["screen"] and stats["read2"]["screen"] are its dicts."""
     if dedup:
         _check_dedup_args(dedup_key_bases, dedup_prefer)
+    if screen is not None:
+        _check_screen(screen, cols1)
     if kmers is not None:
         _check_int("kmers", kmers, 1, _lib.KMER_MAX_K)
     _check_pair_args(cols1, cols2, pair_min_overlap, pair_max_mismatches, pair_max_error_permille, rules.get("min_length", 1))
@@ -595,6 +612,10 @@ def filter_pairs(handle: _lib.Handle, cols1: RecordColumns, cols2: RecordColumns
             begin, end, keep, a_stats = adapter_plan(handle, cols, codes, begin, end, keep, adapter_min_overlap, adapter_max_error_permille,
                                                      rules.get("min_length", 1))
             side = dict(side, adapter=a_stats)
+        if screen is not None:
+            begin, end, keep, s_stats = kmer_plan(handle, cols, begin=begin, end=end, keep=keep,
+                                                  **dict(dict(min_length=rules.get("min_length", 1)), **screen))
+            side = dict(side, screen=s_stats)
         plans.append((begin, end, keep)); stats[name] = side
     merged = None
     if merge:
@@ -814,3 +835,106 @@ def count_kmers(handle: _lib.Handle, cols: RecordColumns, k: int, begin=None, en
     if stats["overflow"]:
         raise RuntimeError("k-mer count: %d occurrences lost to overflow" % stats["overflow"])
     return table, stats
+
+
+# ---- k-mer plan (dsrcgpu_columns_kmer_plan) --------------------------------------------------------------------------------------------
+_CODE_ALPHABET = "ACGTNRWSKMDVHBYXU.-"
+
+
+def columns_from_sequences(seqs, device="cpu") -> RecordColumns:
+    """Strings over the code alphabet "ACGTNRWSKMDVHBYXU.-" (either case; any other byte becomes code 255) -> RecordColumns on `device`
+    with zero qualities and no titles: a reference (adapters, PhiX, rRNA) that count_kmers takes without a FASTQ.  Pure torch."""
+    if isinstance(seqs, (str, bytes, bytearray)) or not hasattr(seqs, "__iter__"):
+        raise ValueError("seqs is a list of strings")
+    seqs = list(seqs)
+    if any(not isinstance(s, str) for s in seqs):
+        raise ValueError("seqs is a list of strings")
+    table = torch.full((256,), 255, dtype=torch.uint8)
+    for code, ch in enumerate(_CODE_ALPHABET):
+        table[ord(ch)] = code
+        table[ord(ch.lower())] = code
+    raw = [s.encode("latin-1", "replace") for s in seqs]
+    text = torch.frombuffer(bytearray(b"".join(raw)), dtype=torch.uint8) if any(raw) else torch.empty(0, dtype=torch.uint8)
+    bases = table[text.to(torch.int64)]
+    offs = torch.zeros(len(raw) + 1, dtype=torch.int64)
+    if raw:
+        offs[1:] = torch.cumsum(torch.tensor([len(s) for s in raw], dtype=torch.int64), 0)
+    device = torch.device(device)
+    u8 = dict(dtype=torch.uint8, device=device); i64 = dict(dtype=torch.int64, device=device)
+    return RecordColumns(bases.to(device), torch.zeros(bases.numel(), **u8), torch.empty(0, **u8), offs.to(device), torch.empty(0, **i64),
+                         torch.tensor([0, len(raw)], **i64))
+
+
+def _check_kmer_plan_args(min_count, min_hits, max_hits, min_hit_permille, max_hit_permille, min_median, max_median, trim, min_length):
+    _check_int("min_count", min_count, 1, (1 << 64) - 1)
+    _check_int("min_hits", min_hits, 0, 0xFFFFFFFE)
+    _check_int("min_hit_permille", min_hit_permille, 0, 1000)
+    _check_int("max_hit_permille", max_hit_permille, 0, 1000)
+    _check_int("min_median", min_median, 0, _lib.KMER_PLAN_COUNT_CAP)
+    _check_int("min_length", min_length, 0, 0xFFFFFFFF)
+    if max_hits is not None:
+        _check_int("max_hits", max_hits, 0, 0xFFFFFFFE)
+    if max_median is not None:
+        _check_int("max_median", max_median, 0, 0xFFFFFFFE)
+    if not isinstance(trim, str) or trim not in _lib.KMER_PLAN_TRIM:
+        raise ValueError("trim must be one of %s" % ", ".join(repr(k) for k in _lib.KMER_PLAN_TRIM))
+
+
+def kmer_plan(handle: _lib.Handle, cols: RecordColumns, table, begin=None, end=None, keep=None, min_count: int = 1, min_hits: int = 0,
+              max_hits=None, min_hit_permille: int = 0, max_hit_permille: int = 1000, min_median: int = 0, max_median=None, trim: str = "none",
+              min_length: int = 1, return_counts: bool = False):
+    """dsrcgpu_columns_kmer_plan on the records of `cols`: every window of k bases of a considered record's range (the plan begin / end
+    / keep; None: whole reads, every record; as the planners return them) is looked up in `table`, a KmerTable of count_kmers on the
+    device of the columns, which is only read -> (begin, end, keep, stats[, good, hits, median]) in fresh tensors.  A window HITS iff
+    its k-mer's count is at least min_count; a window with a code other than A C G T never hits.  A record is kept iff it came in
+    kept, min_hits <= hits <= max_hits, min_hit_permille <= 1000 * hits / windows <= max_hit_permille, min_median <= median <=
+    max_median and at least min_length bases are left.  trim="first_miss": the range ends in front of the last base of the first
+    window that does not hit (khmer's abundance trim, with the table of the batch itself and min_count=2, say); "first_hit": it ends in
+    front of the first window that hits (BBDuk's ktrim=r against a table of adapters).  A contaminant screen is max_hits=0 against the
+    table of count_kmers(columns_from_sequences(reference)).  The median (of the counts capped at 65535, the upper one of two) is taken
+    only when a median bound or return_counts asks for it.  stats is a dict with the keys of _lib.KMER_PLAN_STATS; good, hits,
+    median are int64, one per record.  Arguments out of range raise ValueError before the library is called.  Nothing of the payload
+    crosses to the host."""
+    _check_kmer_plan_args(min_count, min_hits, max_hits, min_hit_permille, max_hit_permille, min_median, max_median, trim, min_length)
+    device = cols.bases.device
+    R = cols.n_records
+    if not isinstance(table, KmerTable) or table.data.dtype != torch.int64 or table.data.device != device or not table.data.is_contiguous() or \
+            table.data.numel() < _lib.kmer_words(16):
+        raise ValueError("table is a KmerTable on the device of the columns")
+    if (begin is None) != (end is None):
+        raise ValueError("begin and end go together")
+    if begin is not None:
+        begin = begin.to(torch.int64).contiguous(); end = end.to(torch.int64).contiguous()
+    if keep is not None:
+        keep = keep.to(torch.uint8).contiguous()
+    for t in (begin, end, keep):
+        if t is not None and (t.numel() != R or t.device != device):
+            raise ValueError("begin, end and keep have one entry per record, on the device of the columns")
+    want_median = bool(return_counts) or min_median != 0 or max_median is not None
+    cin, held = _columns_in(cols, titles=False)
+    adr = lambda t: None if t is None or not t.numel() else t.data_ptr()
+    i64 = dict(dtype=torch.int64, device=device)
+    out_begin = torch.empty(R, **i64); out_end = torch.empty(R, **i64)
+    out_keep = torch.empty(R, dtype=torch.uint8, device=device)
+    good, hits, median = (torch.empty(R, **i64) for _ in range(3)) if return_counts else (None, None, None)
+    rules = _lib.KmerPlanRules(min_count, min_hits, max_hits, min_hit_permille, max_hit_permille, min_median, max_median, _lib.KMER_PLAN_TRIM[trim],
+                               min_length, int(want_median))
+    _quiesce(device)
+    stats = handle.columns_kmer_plan(cin, rules, table.data.data_ptr(), adr(begin), adr(end), adr(keep), adr(out_begin), adr(out_end), adr(out_keep),
+                                     adr(good), adr(hits), adr(median))
+    del held
+    got = (out_begin, out_end, out_keep, dict(zip(_lib.KMER_PLAN_STATS, stats)))
+    return got + (good, hits, median) if return_counts else got
+
+
+def _check_screen(screen, cols):
+    """The `screen` dict of filter_columns / filter_pairs: the keywords of kmer_plan, `table` among them."""
+    allowed = ("table", "min_count", "min_hits", "max_hits", "min_hit_permille", "max_hit_permille", "min_median", "max_median", "trim", "min_length")
+    if not isinstance(screen, dict) or "table" not in screen or any(key not in allowed for key in screen):
+        raise ValueError("screen is a dict of kmer_plan keywords (%s) that holds a table" % ", ".join(allowed))
+    table = screen["table"]
+    if not isinstance(table, KmerTable) or table.data.device != cols.bases.device:
+        raise ValueError("screen['table'] is a KmerTable on the device of the columns")
+    kw = dict(min_count=1, min_hits=0, max_hits=None, min_hit_permille=0, max_hit_permille=1000, min_median=0, max_median=None, trim="none", min_length=1)
+    kw.update({key: v for key, v in screen.items() if key != "table"})
+    _check_kmer_plan_args(**kw)

@@ -53,6 +53,7 @@
 #include "k_columns_dedup.h"
 #include "k_columns_profile.h"
 #include "k_columns_kmer.h"
+#include "k_columns_kmer_plan.h"
 
 namespace
 {
@@ -2873,6 +2874,86 @@ int dsrcgpu_kmer_lookup(dsrcgpu_handle* h, const uint64_t* d_table, const uint64
 	hipLaunchKernelGGL(k_kmer_lookup, dim3((u32)std::max<u64>(1, std::min<u64>(4096, (n + WG - 1) / WG))), dim3(WG), 0, s, t, k, canonical, d_kmers, n, d_counts, d_res); KCHK();
 	HIPCHK(hipMemcpyAsync(invalid, d_res, 8, hipMemcpyDeviceToHost, s));
 	HIPCHK(hipStreamSynchronize(s));
+	return DSRCGPU_OK;
+}
+
+// the k-mer plan (k_columns_kmer_plan.h): the table's header comes home as for a lookup, then the check pass of the adapter plan and
+// the planner run back to back.  Under want_median the error word and the most windows of any considered record come home in
+// between: records with more windows than a wave keeps in LDS get a slice of arena scratch per wave of the grid, and the grid is
+// cut down so that the slices stay under KPLAN_SPILL_BYTES (fewer waves in flight, the same result).
+int dsrcgpu_columns_kmer_plan(dsrcgpu_handle* h, const dsrcgpu_columns_in* in, const dsrcgpu_kmer_plan_rules* rules, const uint64_t* d_table,
+							  const uint64_t* d_begin_in, const uint64_t* d_end_in, const uint8_t* d_keep_in,
+							  uint64_t* d_begin, uint64_t* d_end, uint8_t* d_keep, uint64_t* d_good, uint64_t* d_hits, uint64_t* d_median,
+							  uint64_t stats[16])
+{
+	if (!h) return DSRCGPU_E_ARG;
+	if (!rules || !stats || !d_table) return fail(h, DSRCGPU_E_ARG, "null argument");
+	static_assert(KMER_PLAN_LDS_WINDOWS == DSRCGPU_KMER_PLAN_LDS_WINDOWS && KMER_PLAN_COUNT_CAP == DSRCGPU_KMER_PLAN_COUNT_CAP, "the header's figures are the kernel's");
+	for (u32 i = 0; i < KPLAN_N_STATS; ++i) stats[i] = 0;
+	ColIn c;
+	{ const int rc = sel_in_args(h, in, false, c, false); if (rc) return rc; }
+	if (rules->min_count < 1) return fail(h, DSRCGPU_E_ARG, "kmer plan rules: min_count must be at least 1");
+	if (rules->min_hit_permille > 1000 || rules->max_hit_permille > 1000) return fail(h, DSRCGPU_E_ARG, "kmer plan rules: a permille above 1000");
+	if (rules->trim > KPLAN_TRIM_FIRST_HIT) return fail(h, DSRCGPU_E_ARG, "kmer plan rules: trim must be 0, 1 or 2");
+	if (rules->want_median > 1) return fail(h, DSRCGPU_E_ARG, "kmer plan rules: want_median must be 0 or 1");
+	if (!rules->want_median && (rules->min_median != 0 || rules->max_median != KMER_PLAN_NO_LIMIT || d_median))
+		return fail(h, DSRCGPU_E_ARG, "kmer plan rules: a median bound or d_median without want_median");
+	if (rules->reserved[0] | rules->reserved[1] | rules->reserved[2] | rules->reserved[3]) return fail(h, DSRCGPU_E_ARG, "kmer plan rules: reserved fields must be 0");
+	if (!d_begin_in != !d_end_in) return fail(h, DSRCGPU_E_ARG, "columns: d_begin_in and d_end_in go together");
+	if (c.n_recs && (!d_begin || !d_end || !d_keep)) return fail(h, DSRCGPU_E_ARG, "null argument");
+	HIPCHK(hipSetDevice(h->device));
+	hipStream_t s = h->stream;
+	u64 hdr[8]; KmerTab t; u32 k, canonical;
+	{ const int rc = kmer_table_home(h, d_table, "kmer plan", hdr, t, k, canonical); if (rc) return rc; }
+	if (c.n_recs == 0) return DSRCGPU_OK;
+	const bool median = rules->want_median != 0;
+	const size_t res_bytes = (2 + KPLAN_N_STATS) * 8;     // the error word, the sixteen statistics, the most windows of a record
+	{ const int rc = ensure_arena(h, res_bytes + 1024); if (rc) return rc; }
+	size_t o_res = h->arena.alloc(res_bytes);
+	if (h->arena.failed) return fail(h, DSRCGPU_E_NOMEM, "arena exhausted (kmer plan)");
+	u64* d_res = AP<u64>(h, o_res);
+	HIPCHK(hipMemsetAsync(d_res, 0xFF, 8, s));
+	HIPCHK(hipMemsetAsync(d_res + 1, 0, res_bytes - 8, s));
+	const AdaptPlanIn w{d_begin_in, d_end_in, d_keep_in};
+	const u64 wpg = WG / 64;
+	const dim3 g_check((u32)std::max<u64>(1, std::min<u64>(1024, (c.n_recs + WG - 1) / WG)));
+	u64 gx = std::max<u64>(1, std::min<u64>(4096, (c.n_recs + wpg - 1) / wpg));
+	hipLaunchKernelGGL(k_adapt_check, g_check, dim3(WG), 0, s, c, w, d_res); KCHK();
+	u16* d_spill = nullptr;
+	u64 stride = 0;
+	if (median)
+	{
+		hipLaunchKernelGGL(k_kmer_plan_longest, g_check, dim3(WG), 0, s, c, w, k, d_res + 1 + KPLAN_N_STATS, d_res); KCHK();
+		u64 first[2 + KPLAN_N_STATS];
+		HIPCHK(hipMemcpyAsync(first, d_res, sizeof(first), hipMemcpyDeviceToHost, s));
+		HIPCHK(hipStreamSynchronize(s));
+		if (first[0] != COLE_NONE) return sel_input_error(h, first[0]);
+		const u64 longest = first[1 + KPLAN_N_STATS];
+		if (longest > KMER_PLAN_LDS_WINDOWS)
+		{
+			stride = (longest + 63) & ~63ull;
+			const u64 per_group = stride * 2 * wpg;
+			gx = std::max<u64>(1, std::min<u64>(gx, KPLAN_SPILL_BYTES / per_group));
+			// the arena starts again (it may move): the error word is known to be clean and is set up anew
+			{ const int rc = ensure_arena(h, res_bytes + (size_t)(gx * per_group) + 1024); if (rc) return rc; }
+			o_res = h->arena.alloc(res_bytes);
+			const size_t o_spill = h->arena.alloc((size_t)(gx * per_group));
+			if (h->arena.failed) return fail(h, DSRCGPU_E_NOMEM, "arena exhausted (kmer plan)");
+			d_res = AP<u64>(h, o_res); d_spill = AP<u16>(h, o_spill);
+			HIPCHK(hipMemsetAsync(d_res, 0xFF, 8, s));
+			HIPCHK(hipMemsetAsync(d_res + 1, 0, res_bytes - 8, s));
+		}
+	}
+	const KmerPlanRules R{rules->min_count, rules->min_hits, rules->max_hits, rules->min_hit_permille, rules->max_hit_permille, rules->min_median,
+	                      rules->max_median, rules->trim, rules->min_length};
+	const KmerPlanOut o{d_begin, d_end, d_keep, d_good, d_hits, d_median};
+	if (median) { hipLaunchKernelGGL(k_kmer_plan<true>, dim3((u32)gx), dim3(WG), 0, s, c, w, k, canonical, t, R, o, d_spill, stride, d_res + 1, d_res); KCHK(); }
+	else { hipLaunchKernelGGL(k_kmer_plan<false>, dim3((u32)gx), dim3(WG), 0, s, c, w, k, canonical, t, R, o, d_spill, stride, d_res + 1, d_res); KCHK(); }
+	u64 res[1 + KPLAN_N_STATS];
+	HIPCHK(hipMemcpyAsync(res, d_res, sizeof(res), hipMemcpyDeviceToHost, s));
+	HIPCHK(hipStreamSynchronize(s));
+	if (res[0] != COLE_NONE) return sel_input_error(h, res[0]);
+	for (u32 i = 0; i < KPLAN_N_STATS; ++i) stats[i] = res[1 + i];
 	return DSRCGPU_OK;
 }
 

@@ -596,8 +596,8 @@ int dsrcgpu_columns_profile(dsrcgpu_handle* h, const dsrcgpu_columns_in* in,
  * without a window, [3] windows, [4] k-mers counted, [5] broken windows, [6] keys new to the table, [7] overflow, [8] distinct keys
  * after the call, [9] occurrences in the table after the call, [10 .. 15] 0.  [3] == [4] + [5] + [7].
  * n_records == 0: DSRCGPU_OK; the table is initialised under accumulate = 0 and only checked under 1.
- * Not done here: k above 31, minimizers, per-read annotations (median abundance, digital normalisation, contaminant keep flags: a
- * fifth planner can sit on dsrcgpu_kmer_lookup), approximate counting (Bloom filters, count-min), tables that span several GPUs
+ * Not done here: k above 31, minimizers, per-read annotations (hits, median abundance, contaminant keep flags and the abundance trim
+ * are dsrcgpu_columns_kmer_plan below, which reads this table), approximate counting (Bloom filters, count-min), tables that span several GPUs
  * (dsrcgpu_kmer_table_merge sums the tables of ranks), anything that reorders records.
  * On any error the table is untouched.  DSRCGPU_E_ARG: k 0 or above 31; canonical or accumulate above 1; hash_bits above 64; a
  * capacity that is no power of two in 16 .. 2^40; a non-zero reserved field; a half-given range pair; a null d_table, rules, stats
@@ -647,6 +647,86 @@ int dsrcgpu_kmer_spectrum(dsrcgpu_handle* h, const uint64_t* d_table, uint32_t n
  * is not in the table.  Under a canonical table a query is canonicalised first: a k-mer and its reverse complement give the same
  * answer.  A word >= 4^k gets 0 and is counted in *invalid (host).  The walk is the insert's, without a write. */
 int dsrcgpu_kmer_lookup(dsrcgpu_handle* h, const uint64_t* d_table, const uint64_t* d_kmers, uint64_t n, uint64_t* d_counts, uint64_t* invalid);
+
+/* dsrcgpu_columns_kmer_plan: the fifth planner -- every window of every considered record is looked up in a table of
+ * dsrcgpu_columns_kmer_count, and the record gets a narrowed plan and three annotations.  Two uses: a contaminant screen (count a
+ * reference -- PhiX, rRNA, adapter dimers -- into a table, then drop or cut the reads that hit it: BBDuk), and an abundance trim (count
+ * the batch itself, then cut every read at its first k-mer seen fewer than min_count times: khmer filter-abund / trim-low-abund).
+ * Conventions as dsrcgpu_columns_adapter_plan: the handle's own lane and stream, scratch from the arena (a few words; under want_median
+ * also 2 bytes per window of the longest range for every wave in flight, if a range has more than DSRCGPU_KMER_PLAN_LDS_WINDOWS windows),
+ * synchronised before it returns, codec state left alone, a colour-space handle: DSRCGPU_E_ARG.  Of `in`, d_bases and d_seq_offs are
+ * read; everything else may be NULL.  k and canonical are the table's (its header is read as dsrcgpu_kmer_lookup reads it; a header
+ * that is no table's: DSRCGPU_E_ARG); windows, base codes, broken windows and keys are those of dsrcgpu_columns_kmer_count.  The table
+ * is ONLY READ: not a word of it is written, no atomic touches it.  The plan in: d_begin_in / d_end_in (both NULL = whole reads, one
+ * without the other: DSRCGPU_E_ARG), d_keep_in (NULL = every record; any non-zero byte considers the record).
+ *   for r = 0 .. n_records - 1:
+ *     b, e = the incoming range (whole read if NULL)
+ *     if d_keep_in and d_keep_in[r] == 0:
+ *       d_begin[r] = b; d_end[r] = e; d_keep[r] = 0; good = hits = median = 0; stats[1] += 1; next r
+ *     stats[0] += 1; n = e - b; W = n >= k ? n - k + 1 : 0; if W == 0: stats[2] += 1
+ *     good = hits = 0; first_miss = first_hit = W; C = []
+ *     for p = 0 .. W - 1:
+ *       if any of d_bases[b + p .. b + p + k) is above 3:      hit = false         (a BROKEN window: no hit, not in the median)
+ *       else: good += 1; c = count of key (0 if absent); C += min(c, 65535); hit = c >= min_count
+ *       if hit: hits += 1; first_hit = min(first_hit, p)   else: first_miss = min(first_miss, p)
+ *     median = want_median and good > 0 ? sorted(C)[good / 2] : 0                   (khmer's median: the upper one of two)
+ *     e' = e
+ *     if trim == 1 and first_miss < W: e' = b + first_miss + k - 1                  (khmer: the bases in front of the first bad k-mer's last base)
+ *     if trim == 2 and first_hit  < W: e' = b + first_hit                           (BBDuk ktrim=r: the k-mer and everything behind it go)
+ *     stats[3] += W; stats[4] += good; stats[5] += hits; if hits > 0: stats[7] += 1
+ *     if e' < e: stats[8] += 1; stats[9] += e - e'                                  (kept or not)
+ *     reason = first that fails of:
+ *       [10] min_hits <= hits <= max_hits
+ *       [11] W * min_hit_permille <= hits * 1000 <= W * max_hit_permille
+ *       [12] min_median <= median <= max_median           (only under want_median)
+ *       [13] e' - b >= min_length
+ *     d_begin[r] = b; d_end[r] = e'; d_keep[r] = no reason; stats[reason] += 1, or stats[6] += 1 and stats[14] += e' - b
+ *     d_good[r] = good; d_hits[r] = hits; d_median[r] = median                      (each only if its array is given)
+ * The keep rules judge the range as it CAME: hits, the share of ALL W windows (broken ones included) and the median are taken before the
+ * cut; only min_length sees the cut.  A record without a window has 0 hits of 0 windows: it passes [11] whatever the bounds, fails [10]
+ * under min_hits > 0 and has median 0.  Screening OUT is max_hits = 0 (or max_hit_permille); screening IN is min_hits.
+ * The median is that of the counts CAPPED at DSRCGPU_KMER_PLAN_COUNT_CAP = 65535; min_count sees the raw 64-bit count.
+ * A table with overflow (header word 4) reads a key it lost as absent, count 0: present means exact, absent means 0.
+ * d_good, d_hits, d_median may be NULL, each on its own (d_median must be NULL under want_median = 0).  Aliasing as
+ * dsrcgpu_columns_adapter_plan: a record's incoming plan is read before its outgoing one is written and no other record's is touched,
+ * so d_begin may be d_begin_in, d_end d_end_in and d_keep d_keep_in; in every other way the outputs must not overlap the inputs, the
+ * table or each other; this is not checked.
+ * stats (host): [0] records considered, [1] records that came in dropped, [2] considered records without a window, [3] windows, [4] good
+ * windows, [5] hits, [6] records kept, [7] considered records with at least one hit, [8] records trimmed, [9] bases cut, [10] .. [13]
+ * records dropped, by reason as in the loop, [14] bases in the ranges of kept records, [15] 0.  [0] == [6] + [10] + [11] + [12] + [13]
+ * and [3] >= [4] >= [5].  Sums of integers: the result does not depend on the order in which the device takes the records.
+ * n_records == 0: DSRCGPU_OK, stats 0.
+ * DSRCGPU_E_ARG, nothing written: min_count 0; a permille above 1000; trim above 2; want_median above 1, or 0 together with a median
+ * bound (min_median != 0, max_median != 0xFFFFFFFF) or d_median; a non-zero reserved field; a half-given range pair; a null d_begin,
+ * d_end, d_keep, d_table, rules or stats; a header that is no table's.
+ * DSRCGPU_E_INPUT (outputs untouched; lowest record and reason in dsrcgpu_last_error), for kept and dropped records alike, exactly as
+ * dsrcgpu_columns_adapter_plan: d_seq_offs out of order, a closing entry above bases_len, d_begin_in[r] < S[r], d_end_in[r] > S[r + 1],
+ * d_begin_in[r] > d_end_in[r].  No input makes a kernel read outside the caller's arrays and the table's words, or write outside the
+ * n_records entries of each output.
+ * Not done here: digital normalisation (a read is judged against the counts of the reads kept before it: sequential by nature), a
+ * left-side k-trim (ktrim=l), a mismatch-tolerant lookup (BBDuk's hdist / edist), masking (kmask), any pair rule (two calls; the pair
+ * plan, or keep1 & keep2, joins the sides). */
+#define DSRCGPU_KMER_PLAN_COUNT_CAP 65535
+#define DSRCGPU_KMER_PLAN_LDS_WINDOWS 1024                /* ranges of up to this many windows keep their counts on chip under want_median */
+typedef struct dsrcgpu_kmer_plan_rules
+{
+	uint64_t min_count;          /* >= 1: a window HITS iff the table's count of its key is >= min_count */
+	uint32_t min_hits, max_hits; /* keep iff min_hits <= hits <= max_hits; 0xFFFFFFFF = no upper limit */
+	uint32_t min_hit_permille, max_hit_permille;   /* 0 .. 1000, of ALL the record's windows */
+	uint32_t min_median, max_median;               /* of the capped counts of the good windows; 0xFFFFFFFF = no upper limit */
+	uint32_t trim;               /* 0 none, 1 at the first window that does not hit, 2 at the first window that hits */
+	uint32_t min_length;
+	uint32_t want_median;        /* 0: the median is not computed; d_median must be NULL, min_median 0, max_median 0xFFFFFFFF */
+	uint32_t reserved[4];        /* must be 0 */
+} dsrcgpu_kmer_plan_rules;
+
+int dsrcgpu_columns_kmer_plan(dsrcgpu_handle* h, const dsrcgpu_columns_in* in,
+		const dsrcgpu_kmer_plan_rules* rules,
+		const uint64_t* d_table                        /* device: a table of dsrcgpu_columns_kmer_count, only read */,
+		const uint64_t* d_begin_in, const uint64_t* d_end_in, const uint8_t* d_keep_in   /* device, may be NULL */,
+		uint64_t* d_begin, uint64_t* d_end, uint8_t* d_keep                              /* device, n_records each */,
+		uint64_t* d_good, uint64_t* d_hits, uint64_t* d_median                           /* device, n_records each, each may be NULL */,
+		uint64_t stats[16]);
 
 /* Queue form of DsrcCompressor::Process (src/DsrcWorker.cpp:39-70):
  *   fastqQueue.Pop(partId, chunk)            -> dsrcgpu_submit(partId, chunk)      (bytes are copied into page-locked staging)
