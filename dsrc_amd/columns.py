@@ -128,6 +128,30 @@ def _quiesce(device):       # as in decode_columns: the library works on its own
         torch.cuda.current_stream(device).synchronize()
 
 
+def _adr(t):
+    """The device address of a tensor; None for no tensor and for an empty one."""
+    return None if t is None or not t.numel() else t.data_ptr()
+
+
+def _together(*ranges):
+    if any((begin is None) != (end is None) for begin, end in ranges):
+        raise ValueError("begin and end go together")
+
+
+def _stage_plan(n, device, ranges, keep, insert=None):
+    """A plan as the library takes it: `ranges` is a list of (begin, end) pairs, one per side, each both given or both None; `keep` and
+    (merge_pairs) `insert` are tensors or None.  Checks that the ends go together, brings what is given to contiguous int64 / uint8 and
+    checks that it has n entries on `device` -> (addresses, held): the device addresses in the order begin, end of every side[, insert],
+    keep -- None for what is absent or empty --, and the tensors to keep alive while the addresses are in use."""
+    _together(*ranges)
+    held = [None if t is None else t.to(torch.int64).contiguous() for t in [t for r in ranges for t in r] + ([] if insert is None else [insert])]
+    held.append(None if keep is None else keep.to(torch.uint8).contiguous())
+    if any(t is not None and (t.numel() != n or t.device != device) for t in held):
+        raise ValueError("begin, end, keep and insert have one entry per pair, on the device of the columns" if insert is not None else
+                         "begin, end and keep have one entry per record, on the device of the columns")
+    return [_adr(t) for t in held], held
+
+
 def trim_plan(handle: _lib.Handle, cols: RecordColumns, quality_5: int = 0, quality_3: int = 0, min_length: int = 1, max_n=None,
               min_mean_quality: int = 0):
     """dsrcgpu_columns_trim_plan on the records of `cols`: -> (begin, end, keep, stats).  begin / end (int64) are the kept range of
@@ -153,22 +177,14 @@ def select_columns(handle: _lib.Handle, cols: RecordColumns, begin=None, end=Non
     begin / end are int64 (or uint64-valued) tensors, keep a uint8 or bool tensor, as trim_plan returns them.  The first library call
     sizes the arrays, the second one fills them."""
     device = cols.bases.device
-    if (begin is None) != (end is None):
-        raise ValueError("begin and end go together")
+    _together((begin, end))                                  # (in front of the titles check of _columns_in)
     cin, held = _columns_in(cols, titles)
-    if begin is not None:
-        begin = begin.to(torch.int64).contiguous(); end = end.to(torch.int64).contiguous()
-    if keep is not None:
-        keep = keep.to(torch.uint8).contiguous()
-    for t in (begin, end, keep):
-        if t is not None and (t.numel() != cols.n_records or t.device != device):
-            raise ValueError("begin, end and keep have one entry per record, on the device of the columns")
-    adr = lambda t: None if t is None or not t.numel() else t.data_ptr()
+    plan, plan_held = _stage_plan(cols.n_records, device, [(begin, end)], keep)
     spare = held[-1]
     _quiesce(device)
     need = [0, 0, 0]
     try:
-        handle.columns_select_device(cin, adr(begin), adr(end), adr(keep), _lib.Columns(d_titles=spare.data_ptr() if titles else None))
+        handle.columns_select_device(cin, *plan, _lib.Columns(d_titles=spare.data_ptr() if titles else None))
     except _lib.DsrcGpuError as e:
         if e.code != _lib.E_CAPACITY:
             raise
@@ -184,9 +200,9 @@ def select_columns(handle: _lib.Handle, cols: RecordColumns, begin=None, end=Non
     out = _lib.Columns(ptr(bases), S, ptr(quals), S, ptr(title_bytes) if titles else None, T if titles else 0,
                        seq_offsets.data_ptr(), title_offsets.data_ptr() if titles else None, K)
     _quiesce(device)
-    totals = handle.columns_select_device(cin, adr(begin), adr(end), adr(keep), out, adr(source) if return_source else None)
+    totals = handle.columns_select_device(cin, *plan, out, _adr(source) if return_source else None)
     assert totals == need
-    del held
+    del held, plan_held
     got = RecordColumns(bases, quals, title_bytes, seq_offsets, title_offsets, torch.tensor([0, K], **i64))
     return (got, source) if return_source else got
 
@@ -233,27 +249,17 @@ def adapter_plan(handle: _lib.Handle, cols: RecordColumns, adapters, begin=None,
                             ("min_length", min_length, 0, 0xFFFFFFFF)):
         if not isinstance(v, int) or not lo <= v <= hi:
             raise ValueError("%s must be an integer in %d..%d" % (name, lo, hi))
-    if (begin is None) != (end is None):
-        raise ValueError("begin and end go together")
     device = cols.bases.device
     R = cols.n_records
+    plan, plan_held = _stage_plan(R, device, [(begin, end)], keep)
     cin, held = _columns_in(cols, titles=False)
-    if begin is not None:
-        begin = begin.to(torch.int64).contiguous(); end = end.to(torch.int64).contiguous()
-    if keep is not None:
-        keep = keep.to(torch.uint8).contiguous()
-    for t in (begin, end, keep):
-        if t is not None and (t.numel() != R or t.device != device):
-            raise ValueError("begin, end and keep have one entry per record, on the device of the columns")
-    adr = lambda t: None if t is None or not t.numel() else t.data_ptr()
     out_begin = torch.empty(R, dtype=torch.int64, device=device); out_end = torch.empty(R, dtype=torch.int64, device=device)
     out_keep = torch.empty(R, dtype=torch.uint8, device=device)
     which = torch.empty(R, dtype=torch.int32, device=device) if return_which else None
     rules = _lib.AdapterRules(codes, min_overlap, max_error_permille, min_length)
     _quiesce(device)
-    stats = handle.columns_adapter_plan(cin, rules, adr(begin), adr(end), adr(keep), out_begin.data_ptr(), out_end.data_ptr(), out_keep.data_ptr(),
-                                        adr(which))
-    del held
+    stats = handle.columns_adapter_plan(cin, rules, *plan, out_begin.data_ptr(), out_end.data_ptr(), out_keep.data_ptr(), _adr(which))
+    del held, plan_held
     got = (out_begin, out_end, out_keep, dict(zip(_lib.ADAPTER_STATS, stats)))
     return got + (which.to(torch.int64),) if return_which else got
 
@@ -321,21 +327,12 @@ def profile_columns(handle: _lib.Handle, cols: RecordColumns, begin=None, end=No
     words = _lib.profile_words(n_cycles)
     if into is not None and (into.data.dtype != torch.int64 or into.data.numel() != words or into.data.device != device or not into.data.is_contiguous()):
         raise ValueError("into holds %d int64 counts on the device of the columns" % words)
-    if (begin is None) != (end is None):
-        raise ValueError("begin and end go together")
-    if begin is not None:
-        begin = begin.to(torch.int64).contiguous(); end = end.to(torch.int64).contiguous()
-    if keep is not None:
-        keep = keep.to(torch.uint8).contiguous()
-    for t in (begin, end, keep):
-        if t is not None and (t.numel() != R or t.device != device):
-            raise ValueError("begin, end and keep have one entry per record, on the device of the columns")
+    plan, plan_held = _stage_plan(R, device, [(begin, end)], keep)
     cin, held = _columns_in(cols, titles=False)
-    adr = lambda t: None if t is None or not t.numel() else t.data_ptr()
     out = into if into is not None else ColumnsProfile(torch.empty(words, dtype=torch.int64, device=device), n_cycles)
     _quiesce(device)
-    handle.columns_profile(cin, adr(begin), adr(end), adr(keep), _lib.ProfileRules(n_cycles, 1 if into is not None else 0), out.data.data_ptr())
-    del held
+    handle.columns_profile(cin, *plan, _lib.ProfileRules(n_cycles, 1 if into is not None else 0), out.data.data_ptr())
+    del held, plan_held
     return out
 
 
@@ -418,28 +415,18 @@ def pair_plan(handle: _lib.Handle, cols1: RecordColumns, cols2: RecordColumns, p
     plans = []
     for plan in (plan1, plan2):
         begin, end, keep = (None, None, None) if plan is None else plan
-        if (begin is None) != (end is None):
-            raise ValueError("begin and end go together")
-        if begin is not None:
-            begin = begin.to(torch.int64).contiguous(); end = end.to(torch.int64).contiguous()
-        if keep is not None:
-            keep = keep.to(torch.uint8).contiguous()
-        for t in (begin, end, keep):
-            if t is not None and (t.numel() != R or t.device != device):
-                raise ValueError("begin, end and keep have one entry per record, on the device of the columns")
-        plans.append((begin, end, keep))
+        plans.append(_stage_plan(R, device, [(begin, end)], keep))
     cin1, held1 = _columns_in(cols1, titles=False)
     cin2, held2 = _columns_in(cols2, titles=False)
-    adr = lambda t: None if t is None or not t.numel() else t.data_ptr()
     i64 = dict(dtype=torch.int64, device=device)
     out = [torch.empty(R, **i64) for _ in range(4)]
     keep = torch.empty(R, dtype=torch.uint8, device=device)
     insert = torch.empty(R, **i64) if return_insert else None
     rules = _lib.PairRules(min_overlap, max_mismatches, max_error_permille, min_length)
     _quiesce(device)
-    stats = handle.columns_pair_plan(cin1, cin2, rules, tuple(adr(t) for t in plans[0]), tuple(adr(t) for t in plans[1]),
-                                     out[0].data_ptr(), out[1].data_ptr(), out[2].data_ptr(), out[3].data_ptr(), keep.data_ptr(), adr(insert))
-    del held1, held2
+    stats = handle.columns_pair_plan(cin1, cin2, rules, tuple(plans[0][0]), tuple(plans[1][0]),
+                                     out[0].data_ptr(), out[1].data_ptr(), out[2].data_ptr(), out[3].data_ptr(), keep.data_ptr(), _adr(insert))
+    del held1, held2, plans
     got = (out[0], out[1], out[2], out[3], keep, dict(zip(_lib.PAIR_STATS, stats)))
     return got + (insert,) if return_insert else got          # (2^64 - 1 read as int64 is -1)
 
@@ -473,27 +460,19 @@ def dedup_plan(handle: _lib.Handle, cols: RecordColumns, cols2=None, begin=None,
             raise ValueError("both column sets live on one device")
     elif begin2 is not None or end2 is not None:
         raise ValueError("begin2 and end2 need cols2")
-    if (begin is None) != (end is None) or (begin2 is None) != (end2 is None):
-        raise ValueError("begin and end go together")
+    _together((begin, end), (begin2, end2))                  # (in front of the record count)
     if R > 1 << 31:
         raise ValueError("at most 2^31 records in one call")
-    i64s = [None if t is None else t.to(torch.int64).contiguous() for t in (begin, end, begin2, end2)]
-    if keep is not None:
-        keep = keep.to(torch.uint8).contiguous()
-    for t in i64s + [keep]:
-        if t is not None and (t.numel() != R or t.device != device):
-            raise ValueError("begin, end and keep have one entry per record, on the device of the columns")
+    (b1, e1, b2, e2, keep_in), plan_held = _stage_plan(R, device, [(begin, end), (begin2, end2)], keep)
     cin1, held1 = _columns_in(cols, titles=False)
     cin2, held2 = _columns_in(cols2, titles=False) if cols2 is not None else (None, None)
-    adr = lambda t: None if t is None or not t.numel() else t.data_ptr()
     out_keep = torch.empty(R, dtype=torch.uint8, device=device)
     dup_of = torch.empty(R, dtype=torch.int64, device=device) if return_dup_of else None
     copies = torch.empty(R, dtype=torch.int64, device=device) if return_copies else None
     rules = _lib.DedupRules(key_bases, _lib.DEDUP_PREFER[prefer])
     _quiesce(device)
-    stats = handle.columns_dedup_plan(cin1, cin2, rules, (adr(i64s[0]), adr(i64s[1])), (adr(i64s[2]), adr(i64s[3])), adr(keep), adr(out_keep),
-                                      adr(dup_of), adr(copies))
-    del held1, held2
+    stats = handle.columns_dedup_plan(cin1, cin2, rules, (b1, e1), (b2, e2), keep_in, _adr(out_keep), _adr(dup_of), _adr(copies))
+    del held1, held2, plan_held
     got = (out_keep, dict(zip(_lib.DEDUP_STATS, stats)))
     if return_dup_of:
         got += (dup_of,)                                     # (2^64 - 1 read as int64 is -1)
@@ -523,25 +502,17 @@ def merge_pairs(handle: _lib.Handle, cols1: RecordColumns, cols2: RecordColumns,
         raise ValueError("both column sets live on one device")
     if insert is None:
         raise ValueError("insert is needed: the insert sizes of pair_plan(..., return_insert=True)")
-    if (begin1 is None) != (end1 is None) or (begin2 is None) != (end2 is None):
-        raise ValueError("begin and end go together")
     device = cols1.bases.device
     R = cols1.n_records
-    i64s = [None if t is None else t.to(torch.int64).contiguous() for t in (begin1, end1, begin2, end2, insert)]
-    if keep is not None:
-        keep = keep.to(torch.uint8).contiguous()
-    for t in i64s + [keep]:
-        if t is not None and (t.numel() != R or t.device != device):
-            raise ValueError("begin, end, keep and insert have one entry per pair, on the device of the columns")
+    (b1, e1, b2, e2, d_insert, d_keep), plan_held = _stage_plan(R, device, [(begin1, end1), (begin2, end2)], keep, insert)
     cin1, held1 = _columns_in(cols1, titles)
     cin2, held2 = _columns_in(cols2, titles=False)
     spare = held1[-1]
-    adr = lambda t: None if t is None or not t.numel() else t.data_ptr()
     ptr = lambda t: t.data_ptr() if t.numel() else spare.data_ptr()
     u8 = dict(dtype=torch.uint8, device=device); i64 = dict(dtype=torch.int64, device=device)
     merged = torch.empty(R, **u8)
     rules = _lib.MergeRules(min_overlap, max_mismatches, max_error_permille, quality_cap)
-    args = (cin1, cin2, rules, (adr(i64s[0]), adr(i64s[1])), (adr(i64s[2]), adr(i64s[3])), adr(keep), ptr(i64s[4]))
+    args = (cin1, cin2, rules, (b1, e1), (b2, e2), d_keep, d_insert or spare.data_ptr())      # (no pairs: d_insert is still an address)
     _quiesce(device)
     need = [0, 0, 0]
     try:
@@ -559,9 +530,9 @@ def merge_pairs(handle: _lib.Handle, cols1: RecordColumns, cols2: RecordColumns,
     out = _lib.Columns(ptr(bases), S, ptr(quals), S, ptr(title_bytes) if titles else None, T if titles else 0,
                        seq_offsets.data_ptr(), title_offsets.data_ptr() if titles else None, K)
     _quiesce(device)
-    totals, stats = handle.columns_merge_device(*args, out, ptr(merged), adr(source) if return_source else None)
+    totals, stats = handle.columns_merge_device(*args, out, ptr(merged), _adr(source) if return_source else None)
     assert totals == need
-    del held1, held2
+    del held1, held2, plan_held
     got = (RecordColumns(bases, quals, title_bytes, seq_offsets, title_offsets, torch.tensor([0, K], **i64)), merged, dict(zip(_lib.MERGE_STATS, stats)))
     return got + (source,) if return_source else got
 
@@ -801,24 +772,15 @@ def count_kmers(handle: _lib.Handle, cols: RecordColumns, k: int, begin=None, en
         capacity = into.capacity
     if capacity is not None:
         _check_kmer_capacity(capacity)
-    if (begin is None) != (end is None):
-        raise ValueError("begin and end go together")
-    if begin is not None:
-        begin = begin.to(torch.int64).contiguous(); end = end.to(torch.int64).contiguous()
-    if keep is not None:
-        keep = keep.to(torch.uint8).contiguous()
-    for t in (begin, end, keep):
-        if t is not None and (t.numel() != R or t.device != device):
-            raise ValueError("begin, end and keep have one entry per record, on the device of the columns")
+    plan, plan_held = _stage_plan(R, device, [(begin, end)], keep)
     cin, held = _columns_in(cols, titles=False)
-    adr = lambda t: None if t is None or not t.numel() else t.data_ptr()
     new_table = lambda M: KmerTable(torch.empty(_lib.kmer_words(M), dtype=torch.int64, device=device), k, canonical)
     sizing = into is None and capacity is None
     table = into if into is not None else new_table(16 if sizing else capacity)
     _quiesce(device)
 
     def call():
-        return handle.columns_kmer_count(cin, adr(begin), adr(end), adr(keep), _lib.KmerRules(k, int(canonical), 1 if into is not None else 0, 0, table.capacity),
+        return handle.columns_kmer_count(cin, *plan, _lib.KmerRules(k, int(canonical), 1 if into is not None else 0, 0, table.capacity),
                                          table.data.data_ptr())
     try:
         stats = call()
@@ -830,7 +792,7 @@ def count_kmers(handle: _lib.Handle, cols: RecordColumns, k: int, begin=None, en
         else:
             table = new_table(e.need)
         stats = call()
-    del held
+    del held, plan_held
     stats = dict(zip(_lib.KMER_STATS, stats))
     if stats["overflow"]:
         raise RuntimeError("k-mer count: %d occurrences lost to overflow" % stats["overflow"])
@@ -901,18 +863,9 @@ def kmer_plan(handle: _lib.Handle, cols: RecordColumns, table, begin=None, end=N
     if not isinstance(table, KmerTable) or table.data.dtype != torch.int64 or table.data.device != device or not table.data.is_contiguous() or \
             table.data.numel() < _lib.kmer_words(16):
         raise ValueError("table is a KmerTable on the device of the columns")
-    if (begin is None) != (end is None):
-        raise ValueError("begin and end go together")
-    if begin is not None:
-        begin = begin.to(torch.int64).contiguous(); end = end.to(torch.int64).contiguous()
-    if keep is not None:
-        keep = keep.to(torch.uint8).contiguous()
-    for t in (begin, end, keep):
-        if t is not None and (t.numel() != R or t.device != device):
-            raise ValueError("begin, end and keep have one entry per record, on the device of the columns")
+    plan, plan_held = _stage_plan(R, device, [(begin, end)], keep)
     want_median = bool(return_counts) or min_median != 0 or max_median is not None
     cin, held = _columns_in(cols, titles=False)
-    adr = lambda t: None if t is None or not t.numel() else t.data_ptr()
     i64 = dict(dtype=torch.int64, device=device)
     out_begin = torch.empty(R, **i64); out_end = torch.empty(R, **i64)
     out_keep = torch.empty(R, dtype=torch.uint8, device=device)
@@ -920,9 +873,9 @@ def kmer_plan(handle: _lib.Handle, cols: RecordColumns, table, begin=None, end=N
     rules = _lib.KmerPlanRules(min_count, min_hits, max_hits, min_hit_permille, max_hit_permille, min_median, max_median, _lib.KMER_PLAN_TRIM[trim],
                                min_length, int(want_median))
     _quiesce(device)
-    stats = handle.columns_kmer_plan(cin, rules, table.data.data_ptr(), adr(begin), adr(end), adr(keep), adr(out_begin), adr(out_end), adr(out_keep),
-                                     adr(good), adr(hits), adr(median))
-    del held
+    stats = handle.columns_kmer_plan(cin, rules, table.data.data_ptr(), *plan, _adr(out_begin), _adr(out_end), _adr(out_keep),
+                                     _adr(good), _adr(hits), _adr(median))
+    del held, plan_held
     got = (out_begin, out_end, out_keep, dict(zip(_lib.KMER_PLAN_STATS, stats)))
     return got + (good, hits, median) if return_counts else got
 
