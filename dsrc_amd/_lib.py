@@ -29,7 +29,7 @@ EXPORTS = [
     "dsrcgpu_columns_trim_plan", "dsrcgpu_columns_select_device", "dsrcgpu_columns_adapter_plan", "dsrcgpu_columns_pair_plan",
     "dsrcgpu_columns_profile", "dsrcgpu_columns_merge_device", "dsrcgpu_columns_dedup_plan",
     "dsrcgpu_columns_kmer_count", "dsrcgpu_kmer_table_merge", "dsrcgpu_kmer_spectrum", "dsrcgpu_kmer_lookup",
-    "dsrcgpu_columns_kmer_plan",
+    "dsrcgpu_columns_kmer_plan", "dsrcgpu_columns_kmer_correct",
 ]
 
 # error codes of include/dsrc_gpu.h that callers tell apart (DsrcGpuError.code)
@@ -225,6 +225,22 @@ KMER_PLAN_TRIM = {"none": 0, "first_miss": 1, "first_hit": 2}
 KMER_PLAN_STATS = ("records_considered", "records_came_dropped", "records_no_window", "windows", "windows_good", "hits", "records_kept",
                    "records_with_hit", "records_trimmed", "bases_cut", "dropped_hits", "dropped_hit_share", "dropped_median", "dropped_length",
                    "bases_kept")
+
+
+class KmerCorrectRules(C.Structure):
+    """dsrcgpu_kmer_correct_rules: KmerCorrectRules(min_count, max_quality); max_quality None = 255 = a base of any quality may be
+    replaced (the qualities are then not read).  The library is the one that refuses figures out of range."""
+    _fields_ = [("min_count", C.c_uint64), ("max_quality", C.c_uint32), ("reserved", C.c_uint32 * 5)]
+
+    def __init__(self, min_count=2, max_quality=None, reserved=(0, 0, 0, 0, 0)):
+        super().__init__()
+        self.min_count, self.max_quality = min_count, 255 if max_quality is None else max_quality
+        self.reserved = (C.c_uint32 * 5)(*reserved)
+
+
+KMER_CORRECT_STATS = ("records_considered", "records_came_dropped", "records_no_window", "windows", "windows_solid", "runs", "bases_fixed",
+                      "bases_fixed_n", "records_fixed", "runs_whole_range", "runs_long", "runs_short_interior", "runs_no_candidate",
+                      "runs_ambiguous", "runs_quality", "records_all_solid")
 
 
 class HostColumns(typing.NamedTuple):
@@ -673,6 +689,17 @@ class Handle:
         self._chk(self.L.dsrcgpu_columns_kmer_plan(self.h, C.byref(cols_in), C.byref(rules), C.c_void_p(d_table), C.c_void_p(d_begin_in),
                                                    C.c_void_p(d_end_in), C.c_void_p(d_keep_in), C.c_void_p(d_begin), C.c_void_p(d_end),
                                                    C.c_void_p(d_keep), C.c_void_p(d_good), C.c_void_p(d_hits), C.c_void_p(d_median), stats))
+        return list(stats)
+
+    def columns_kmer_correct(self, cols_in: ColumnsIn, rules: KmerCorrectRules, d_table, d_begin, d_end, d_keep, d_bases_out, d_fixed=None):
+        """dsrcgpu_columns_kmer_correct: the substitution errors of the records of `cols_in` under the plan d_begin / d_end / d_keep (device
+        addresses or None: whole reads, every record) repaired against the table d_table (of columns_kmer_count; only read) into
+        d_bases_out, device memory addressed like the bases of `cols_in` -- that very array (in place: only the repaired bytes are
+        written) or another one (the span of the records is copied, with the repairs); d_fixed (uint64, n_records entries, or None)
+        gets the repairs per record.  Returns the sixteen statistics (KMER_CORRECT_STATS names them)."""
+        stats = (C.c_uint64 * 16)()
+        self._chk(self.L.dsrcgpu_columns_kmer_correct(self.h, C.byref(cols_in), C.byref(rules), C.c_void_p(d_table), C.c_void_p(d_begin),
+                                                      C.c_void_p(d_end), C.c_void_p(d_keep), C.c_void_p(d_bases_out), C.c_void_p(d_fixed), stats))
         return list(stats)
 
     def columns_select_device(self, cols_in: ColumnsIn, d_begin, d_end, d_keep, out: Columns, d_source=None):

@@ -1,6 +1,7 @@
 """Records as torch tensors: decode_columns (dsrcgpu_decompress_batch_columns_device), the way back, encode_columns
 (dsrcgpu_compress_columns_device), and what runs between the two: trim_plan (dsrcgpu_columns_trim_plan), adapter_plan
-(dsrcgpu_columns_adapter_plan), kmer_plan (dsrcgpu_columns_kmer_plan, with columns_from_sequences for its reference), pair_plan
+(dsrcgpu_columns_adapter_plan), kmer_plan (dsrcgpu_columns_kmer_plan, with columns_from_sequences for its reference), correct_kmers
+(dsrcgpu_columns_kmer_correct), pair_plan
 (dsrcgpu_columns_pair_plan), dedup_plan (dsrcgpu_columns_dedup_plan), merge_pairs (dsrcgpu_columns_merge_device), select_columns
 (dsrcgpu_columns_select_device), filter_columns and, for paired-end data,
 filter_pairs, the report on either side of them, profile_columns (dsrcgpu_columns_profile), and the k-mer table of a plan, count_kmers
@@ -338,7 +339,7 @@ def profile_columns(handle: _lib.Handle, cols: RecordColumns, begin=None, end=No
 
 def filter_columns(handle: _lib.Handle, cols: RecordColumns, titles: bool = True, adapters=None, adapter_min_overlap: int = 3,
                    adapter_max_error_permille: int = 100, profile: bool = False, dedup: bool = False, dedup_key_bases: int = 0,
-                   dedup_prefer: str = "first", kmers=None, screen=None, **rules):
+                   dedup_prefer: str = "first", kmers=None, screen=None, correct=None, **rules):
     """trim_plan(**rules) and select_columns with its plan in sequence: -> (RecordColumns of the trimmed, kept records, stats).
     adapters (see adapter_plan): between the two, adapter_plan narrows the trim plan -- the quality trim first, the adapter second,
     the order of cutadapt and fastp -- with the same min_length; stats is then the trim plan's dict plus a key "adapter" that holds
@@ -353,11 +354,18 @@ def filter_columns(handle: _lib.Handle, cols: RecordColumns, titles: bool = True
     canonical k-mers of the records that come out, and it needs no select.
     screen (a dict of kmer_plan keywords, its `table` among them): behind the adapter plan and in front of dedup, kmer_plan narrows the
     plan against that table -- a contaminant screen (max_hits=0) or an abundance trim -- with the filter's min_length unless the dict
-    gives one; stats gets "screen", its dict, and profile, kmers and the select see the narrowed plan."""
+    gives one; stats gets "screen", its dict, and profile, kmers and the select see the narrowed plan.
+    correct (a dict: min_count and max_quality of correct_kmers, and either table=a KmerTable or k=an int): behind the adapter plan and
+    in front of the screen, correct_kmers repairs the bases on the ranges and keep at that point -- with k= against the table of
+    count_kmers(k) of the batch under that very plan; stats gets "correct", its dict.  Everything behind it (screen, dedup,
+    "profile_after", "kmers_after", the select) sees the repaired bases; `cols` stays as it is, and "profile_before", and max_n of
+    the trim plan, saw the bases as they came."""
     if adapters is not None:
         codes = _adapter_codes(adapters)
     if screen is not None:
         _check_screen(screen, cols)
+    if correct is not None:
+        _check_correct(correct, cols)
     if kmers is not None:
         _check_int("kmers", kmers, 1, _lib.KMER_MAX_K)
     if dedup:
@@ -367,6 +375,10 @@ def filter_columns(handle: _lib.Handle, cols: RecordColumns, titles: bool = True
         begin, end, keep, a_stats = adapter_plan(handle, cols, codes, begin, end, keep, adapter_min_overlap, adapter_max_error_permille,
                                                  rules.get("min_length", 1))
         stats = dict(stats, adapter=a_stats)
+    came = cols
+    if correct is not None:
+        cols, c_stats = _correct_step(handle, [(cols, begin, end, keep)], correct)[0]
+        stats = dict(stats, correct=c_stats)
     if screen is not None:
         begin, end, keep, s_stats = kmer_plan(handle, cols, begin=begin, end=end, keep=keep,
                                               **dict(dict(min_length=rules.get("min_length", 1)), **screen))
@@ -375,7 +387,7 @@ def filter_columns(handle: _lib.Handle, cols: RecordColumns, titles: bool = True
         keep, d_stats = dedup_plan(handle, cols, begin=begin, end=end, keep=keep, key_bases=dedup_key_bases, prefer=dedup_prefer)
         stats = dict(stats, dedup=d_stats)
     if profile:
-        before = profile_columns(handle, cols)
+        before = profile_columns(handle, came)
         stats = dict(stats, profile_before=before, profile_after=profile_columns(handle, cols, begin, end, keep, n_cycles=before.n_cycles))
     if kmers is not None:
         stats = dict(stats, kmers_after=count_kmers(handle, cols, kmers, begin, end, keep)[0])
@@ -541,7 +553,7 @@ def filter_pairs(handle: _lib.Handle, cols1: RecordColumns, cols2: RecordColumns
                  overlap: bool = True, pair_min_overlap: int = 30, pair_max_mismatches: int = 5, pair_max_error_permille: int = 200,
                  adapter_min_overlap: int = 3, adapter_max_error_permille: int = 100, profile: bool = False, merge: bool = False,
                  merge_quality_cap: int = 41, dedup: bool = False, dedup_key_bases: int = 0, dedup_prefer: str = "first", kmers=None, screen=None,
-                 **rules):
+                 correct=None, **rules):
     """filter_columns for paired-end data: per side trim_plan(**rules) and, if adapters<s> is given, adapter_plan; then pair_plan with
     the same min_length, which cuts read-through found from the overlap of the mates and decides per PAIR; then one select_columns per
     side with that side's ranges and the joint keep -> (out1, out2, stats), out1.n_records == out2.n_records always and record j of
@@ -563,9 +575,14 @@ def filter_pairs(handle: _lib.Handle, cols1: RecordColumns, cols2: RecordColumns
     screen (a dict of kmer_plan keywords, its `table` among them): per side, behind that side's adapter plan and in front of the pair
     plan, kmer_plan narrows the side's plan against that table, with the filter's min_length unless the dict gives one; the pair plan
     (overlap=False: keep1 & keep2) then makes it a decision per PAIR -- a pair goes if either mate is screened out, as in BBDuk.
-    stats["read1"]["screen"] and stats["read2"]["screen"] are its dicts."""
+    stats["read1"]["screen"] and stats["read2"]["screen"] are its dicts.
+    correct (as in filter_columns): per side, behind that side's adapter plan and in front of the screen and the pair plan, correct_kmers
+    repairs the bases; with k= ONE table of both mates under their plans is counted first.  stats["read1"]["correct"] and
+    stats["read2"]["correct"] are its dicts; everything behind it sees the repaired bases, "profile_before" the bases as they came."""
     if dedup:
         _check_dedup_args(dedup_key_bases, dedup_prefer)
+    if correct is not None:
+        _check_correct(correct, cols1)
     if screen is not None:
         _check_screen(screen, cols1)
     if kmers is not None:
@@ -583,11 +600,17 @@ def filter_pairs(handle: _lib.Handle, cols1: RecordColumns, cols2: RecordColumns
             begin, end, keep, a_stats = adapter_plan(handle, cols, codes, begin, end, keep, adapter_min_overlap, adapter_max_error_permille,
                                                      rules.get("min_length", 1))
             side = dict(side, adapter=a_stats)
-        if screen is not None:
+        plans.append((begin, end, keep)); stats[name] = side
+    came1, came2 = cols1, cols2
+    if correct is not None:
+        (cols1, c1_stats), (cols2, c2_stats) = _correct_step(handle, [(cols1,) + plans[0], (cols2,) + plans[1]], correct)
+        stats["read1"] = dict(stats["read1"], correct=c1_stats); stats["read2"] = dict(stats["read2"], correct=c2_stats)
+    if screen is not None:
+        for i, (name, cols) in enumerate((("read1", cols1), ("read2", cols2))):
+            begin, end, keep = plans[i]
             begin, end, keep, s_stats = kmer_plan(handle, cols, begin=begin, end=end, keep=keep,
                                                   **dict(dict(min_length=rules.get("min_length", 1)), **screen))
-            side = dict(side, screen=s_stats)
-        plans.append((begin, end, keep)); stats[name] = side
+            plans[i] = (begin, end, keep); stats[name] = dict(stats[name], screen=s_stats)
     merged = None
     if merge:
         b1, e1, b2, e2, keep, p_stats, insert = pair_plan(handle, cols1, cols2, plans[0], plans[1], pair_min_overlap, pair_max_mismatches,
@@ -608,8 +631,8 @@ def filter_pairs(handle: _lib.Handle, cols1: RecordColumns, cols2: RecordColumns
     if dedup and not merge:
         keep, stats["dedup"] = dedup_plan(handle, cols1, cols2, b1, e1, b2, e2, keep, dedup_key_bases, dedup_prefer)
     if profile:
-        for name, cols, b, e in (("read1", cols1, b1, e1), ("read2", cols2, b2, e2)):
-            before = profile_columns(handle, cols)
+        for name, cols, came, b, e in (("read1", cols1, came1, b1, e1), ("read2", cols2, came2, b2, e2)):
+            before = profile_columns(handle, came)
             stats[name] = dict(stats[name], profile_before=before, profile_after=profile_columns(handle, cols, b, e, keep, n_cycles=before.n_cycles))
     if kmers is not None:
         table, _ = count_kmers(handle, cols1, kmers, b1, e1, keep)
@@ -891,3 +914,70 @@ def _check_screen(screen, cols):
     kw = dict(min_count=1, min_hits=0, max_hits=None, min_hit_permille=0, max_hit_permille=1000, min_median=0, max_median=None, trim="none", min_length=1)
     kw.update({key: v for key, v in screen.items() if key != "table"})
     _check_kmer_plan_args(**kw)
+
+
+# ---- k-mer correction (dsrcgpu_columns_kmer_correct) -----------------------------------------------------------------------------------
+def _check_kmer_correct_args(min_count, max_quality):
+    _check_int("min_count", min_count, 1, (1 << 64) - 1)
+    if max_quality is not None:
+        _check_int("max_quality", max_quality, 0, 255)
+
+
+def correct_kmers(handle: _lib.Handle, cols: RecordColumns, table, begin=None, end=None, keep=None, min_count: int = 2, max_quality=None,
+                  inplace: bool = False, return_fixed: bool = False):
+    """dsrcgpu_columns_kmer_correct on the records of `cols`: isolated substitution errors, and codes other than A C G T, of a considered
+    record's range (the plan begin / end / keep; None: whole reads, every record; as the planners return them) are repaired against
+    `table`, a KmerTable of count_kmers on the device of the columns, which is only read -> (RecordColumns, stats[, fixed]).  A window
+    of k bases is SOLID iff it holds A C G T only and its k-mer's count is at least min_count; an error shows as a run of up to k
+    windows that are not solid, and the base they share is replaced where exactly ONE other base makes every one of them solid (the
+    rule, and what it leaves alone: include/dsrc_gpu.h).  max_quality: a base of a higher quality is never replaced (None: any).
+    The result shares every tensor of `cols` but bases; with inplace=True cols.bases itself is repaired and the result is `cols`.
+    Qualities are not touched.  The usual table is that of the batch itself: count_kmers(handle, cols, 21), then min_count=3, say;
+    the call is idempotent, and a second pass is count_kmers on the result and another call.  stats is a dict with the keys of
+    _lib.KMER_CORRECT_STATS; fixed (int64) is the number of repairs per record.  Arguments out of range raise ValueError before the
+    library is called.  Nothing of the payload crosses to the host."""
+    _check_kmer_correct_args(min_count, max_quality)
+    device = cols.bases.device
+    R = cols.n_records
+    if not isinstance(table, KmerTable) or table.data.dtype != torch.int64 or table.data.device != device or not table.data.is_contiguous() or \
+            table.data.numel() < _lib.kmer_words(16):
+        raise ValueError("table is a KmerTable on the device of the columns")
+    if inplace and not cols.bases.is_contiguous():
+        raise ValueError("inplace=True needs contiguous bases")
+    plan, plan_held = _stage_plan(R, device, [(begin, end)], keep)
+    cin, held = _columns_in(cols, titles=False)
+    out = cols.bases if inplace else held[0].clone()         # (the bytes outside the records' span, if any, are the input's too)
+    spare = torch.empty(8, dtype=torch.uint8, device=device)
+    fixed = torch.empty(R, dtype=torch.int64, device=device) if return_fixed else None
+    _quiesce(device)
+    stats = handle.columns_kmer_correct(cin, _lib.KmerCorrectRules(min_count, max_quality), table.data.data_ptr(), *plan,
+                                        cin.d_bases if inplace else out.data_ptr() if out.numel() else spare.data_ptr(), _adr(fixed))
+    del held, plan_held
+    got = (cols if inplace else dataclasses.replace(cols, bases=out), dict(zip(_lib.KMER_CORRECT_STATS, stats)))
+    return got + (fixed,) if return_fixed else got
+
+
+def _check_correct(correct, cols):
+    """The `correct` dict of filter_columns / filter_pairs: the keywords min_count and max_quality of correct_kmers and either `table`
+    or `k` (the batch is counted under the plan at that point first)."""
+    allowed = ("table", "k", "min_count", "max_quality")
+    if not isinstance(correct, dict) or ("table" in correct) == ("k" in correct) or any(key not in allowed for key in correct):
+        raise ValueError("correct is a dict of correct_kmers keywords (%s) that holds a table or a k" % ", ".join(allowed))
+    if "table" in correct:
+        table = correct["table"]
+        if not isinstance(table, KmerTable) or table.data.device != cols.bases.device:
+            raise ValueError("correct['table'] is a KmerTable on the device of the columns")
+    else:
+        _check_int("k", correct["k"], 1, _lib.KMER_MAX_K)
+    _check_kmer_correct_args(correct.get("min_count", 2), correct.get("max_quality"))
+
+
+def _correct_step(handle, sides, correct):
+    """The `correct` step of the filters: sides = [(cols, begin, end, keep)], one entry or the two mates -> [(repaired cols, stats)].
+    With k= the sides are counted into ONE table under their plans first."""
+    table = correct.get("table")
+    if table is None:
+        for cols, begin, end, keep in sides:
+            table, _ = count_kmers(handle, cols, correct["k"], begin, end, keep, into=table)
+    kw = {key: v for key, v in correct.items() if key in ("min_count", "max_quality")}
+    return [correct_kmers(handle, cols, table, begin, end, keep, **kw) for cols, begin, end, keep in sides]

@@ -54,6 +54,7 @@
 #include "k_columns_profile.h"
 #include "k_columns_kmer.h"
 #include "k_columns_kmer_plan.h"
+#include "k_columns_kmer_correct.h"
 
 namespace
 {

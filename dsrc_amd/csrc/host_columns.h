@@ -808,4 +808,38 @@ int dsrcgpu_columns_kmer_plan(dsrcgpu_handle* h, const dsrcgpu_columns_in* in, c
 	return DSRCGPU_OK;
 }
 
+// the k-mer correction (k_columns_kmer_correct.h): the table's header comes home as for the plan, then the check pass of the adapter
+// plan, out of place the copy of the span, and the corrector run back to back.  Both kernels behind the check pass look at its error
+// word first, so that an input error leaves d_bases_out and d_fixed as they were.
+int dsrcgpu_columns_kmer_correct(dsrcgpu_handle* h, const dsrcgpu_columns_in* in, const dsrcgpu_kmer_correct_rules* rules, const uint64_t* d_table,
+								 const uint64_t* d_begin, const uint64_t* d_end, const uint8_t* d_keep, uint8_t* d_bases_out, uint64_t* d_fixed,
+								 uint64_t stats[16])
+{
+	if (!h) return DSRCGPU_E_ARG;
+	if (!rules || !stats || !d_table || !d_bases_out) return fail(h, DSRCGPU_E_ARG, "null argument");
+	for (u32 i = 0; i < KCORR_N_STATS; ++i) stats[i] = 0;
+	if (rules->max_quality > 255) return fail(h, DSRCGPU_E_ARG, "kmer correct rules: max_quality above 255");
+	ColIn c;
+	if (const int rc = col_in_args(h, in, rules->max_quality < 255 ? COL_QUALS : 0, c)) return rc;
+	if (rules->min_count < 1) return fail(h, DSRCGPU_E_ARG, "kmer correct rules: min_count must be at least 1");
+	if (const int rc = reserved_clear(h, "kmer correct rules", rules->reserved)) return rc;
+	if (const int rc = together(h, d_begin, d_end, "d_begin", "d_end")) return rc;
+	HIPCHK(hipSetDevice(h->device));
+	hipStream_t s = h->stream;
+	u64 hdr[8]; KmerTab t; u32 k, canonical;
+	if (const int rc = kmer_table_home(h, d_table, "kmer correct", hdr, t, k, canonical)) return rc;
+	if (c.n_recs == 0) return DSRCGPU_OK;
+	if (const int rc = ensure_arena(h, (1 + KCORR_N_STATS) * 8 + 1024)) return rc;
+	ResWords res = res_alloc(h, 1, KCORR_N_STATS);        // the error word, the sixteen statistics
+	if (const int rc = res_begin(h, res, "kmer correct")) return rc;
+	const AdaptPlanIn w{d_begin, d_end, d_keep};
+	const KmerCorrectRules R{rules->min_count, rules->max_quality};
+	hipLaunchKernelGGL(k_adapt_check, grid_threads(c.n_recs), dim3(WG), 0, s, c, w, res.d); KCHK();
+	if (d_bases_out != c.bases) { hipLaunchKernelGGL(k_kmer_correct_copy, grid_threads(c.bases_len / 8 + 1, 4096), dim3(WG), 0, s, c, d_bases_out, res.d); KCHK(); }
+	hipLaunchKernelGGL(k_kmer_correct, grid_waves(c.n_recs), dim3(WG), 0, s, c, w, k, canonical, t, R, d_bases_out, d_fixed, res.counters(), res.d); KCHK();
+	if (const int rc = res_home(h, res)) return rc;
+	for (u32 i = 0; i < KCORR_N_STATS; ++i) stats[i] = res.home()[i];
+	return DSRCGPU_OK;
+}
+
 } // extern "C"

@@ -728,6 +728,90 @@ int dsrcgpu_columns_kmer_plan(dsrcgpu_handle* h, const dsrcgpu_columns_in* in,
 		uint64_t* d_good, uint64_t* d_hits, uint64_t* d_median                           /* device, n_records each, each may be NULL */,
 		uint64_t stats[16]);
 
+/* dsrcgpu_columns_kmer_correct: the third thing a k-mer toolkit does with a table -- the reads are REPAIRED against it (Tadpole,
+ * Lighter, BFC, Musket, Quake).  A substitution error turns up to k consecutive windows of a read into k-mers the data set has hardly
+ * seen; where exactly one replacement of the base those windows share makes every one of them solid, that base is put right.  The
+ * second columnar call that writes new bases (dsrcgpu_columns_merge_device was the first) and the first that writes them from evidence
+ * outside the record; it closes decode -> dsrcgpu_columns_kmer_count -> correct -> dsrcgpu_compress_columns_device on one device.
+ * Conventions as dsrcgpu_columns_kmer_plan: the handle's own lane and stream, scratch from the arena (a few words), synchronised before
+ * it returns, codec state left alone, a colour-space handle: DSRCGPU_E_ARG.  Of `in`, d_bases and d_seq_offs are read, and d_quals
+ * under max_quality < 255; everything else may be NULL.  Windows, base codes, broken windows, keys, k and canonical are those of
+ * dsrcgpu_columns_kmer_count and of the table's header, read as dsrcgpu_columns_kmer_plan reads it.  The table is ONLY READ.  The plan
+ * in: d_begin / d_end (both NULL = whole reads, one without the other: DSRCGPU_E_ARG), d_keep (NULL = every record; any non-zero byte
+ * considers the record).
+ * A window is SOLID iff it holds no code above 3 and its key's count is at least min_count.  S = d_seq_offs, bases = in->d_bases,
+ * out = d_bases_out, quals = in->d_quals:
+ *   for r = 0 .. n_records - 1:
+ *     b, e = the incoming range (whole read if NULL)
+ *     out[S[r] .. S[r+1]) = bases[S[r] .. S[r+1])            (see "the output" below)
+ *     if d_keep and d_keep[r] == 0: stats[1] += 1; d_fixed[r] = 0; next r
+ *     stats[0] += 1; n = e - b; W = n >= k ? n - k + 1 : 0
+ *     if W == 0: stats[2] += 1
+ *     solid[w] for w = 0 .. W - 1, all taken from the bases AS THEY CAME
+ *     stats[3] += W; stats[4] += number of solid windows
+ *     if W > 0 and all solid: stats[15] += 1
+ *     fixed = 0
+ *     for every maximal run [w0, w1] of windows that are not solid, len = w1 - w0 + 1:
+ *       stats[5] += 1
+ *       if w0 == 0 and w1 == W - 1:   stats[9]  += 1; next run   (no solid window in the range)
+ *       if len > k:                   stats[10] += 1; next run   (more than one error)
+ *       if w0 == 0:           p = w1                             (the run touches the 5' end)
+ *       else if w1 == W - 1:  p = w0 + k - 1                     (the run touches the 3' end)
+ *       else if len == k:     p = w1                             (interior: == w0 + k - 1)
+ *       else:                 stats[11] += 1; next run           (interior, shorter than k)
+ *       if max_quality < 255 and quals[b + p] > max_quality: stats[14] += 1; next run
+ *       A = { x in 0..3, x != bases[b + p] :
+ *             every window w0 .. w1 is solid once position p reads x }
+ *             (3 candidates for a base, 4 for a code above 3)
+ *       if |A| == 0: stats[12] += 1; next run
+ *       if |A| >= 2: stats[13] += 1; next run
+ *       out[b + p] = the one x; fixed += 1; stats[6] += 1
+ *       if bases[b + p] > 3: stats[7] += 1
+ *     if fixed: stats[8] += 1
+ *     d_fixed[r] = fixed                                         (only if the array is given)
+ * - Every window that contains p lies inside the run, in all three placements.  So runs do not see each other's repairs, and the
+ *   verdicts do not depend on the order of the runs.  A run needs only positions w0 .. w1 + k - 1 of the read, at most 2k - 1 <= 61.
+ * - stats[5] == stats[6] + stats[9] + stats[10] + stats[11] + stats[12] + stats[13] + stats[14].
+ * - Idempotent: a second call on the output with the same table and rules changes nothing, has stats[6] == 0 and finds stats[5]
+ *   smaller by the first call's stats[6] (a repaired run is gone, every other run is as it was).
+ * - Qualities are not touched.  A replaced N keeps its quality, and dsrcgpu_compress_columns_device takes that text as the text call
+ *   does.
+ * - A table with overflow (header word 4) reads a key it lost as absent.
+ * Worked examples: k = 3, forward words, the table of the one read ACGTTGCA, min_count = 1.  ACGTAGCA, TCGTTGCA, AGGTTGCA, ACGTTGCC,
+ * ACGTNGCA and ACNTTGCA each give ACGTTGCA, one run fixed.  ACGAAGCA is unchanged, counted in [10].  TTT is unchanged, counted in
+ * [9].  AC and ACG have no run.  With ACGTCGCA counted into the table as well, ACGTAGCA is unchanged, counted in [13].
+ * THE OUTPUT.  d_bases_out is addressed with the offsets of in->d_seq_offs, like in->d_bases.  Out of place: exactly the bytes
+ * [S[0], S[n_records]) are written, a copy of the input with the repairs -- records that are dropped, out of range or without windows
+ * included; nothing before or behind that span is written.  In place, d_bases_out == in->d_bases: only the repaired positions are
+ * written.  Any other overlap with the inputs, the table or d_fixed is not allowed and not checked.  d_fixed (n_records, may be
+ * NULL): the repairs of every record, 0 for a record that is not considered.
+ * stats (host): [0] records considered, [1] records that came in dropped, [2] considered records without a window, [3] windows, [4]
+ * solid windows, [5] runs, [6] bases repaired, [7] of these, codes above 3, [8] records with a repair, [9] .. [14] runs left alone, by
+ * reason as in the loop, [15] considered records with windows that are all solid.  Sums of integers: the result does not depend on
+ * the order in which the device takes the records.
+ * n_records == 0: DSRCGPU_OK, stats 0, nothing written.
+ * DSRCGPU_E_ARG, nothing written: min_count 0; max_quality above 255; a non-zero reserved field; a half-given range pair; a null in,
+ * rules, d_table, d_bases_out or stats; a null d_quals under max_quality < 255; a header that is no table's.
+ * DSRCGPU_E_INPUT (not a byte of d_bases_out or d_fixed changed; lowest record and reason in dsrcgpu_last_error), for kept and dropped
+ * records alike, exactly as dsrcgpu_columns_kmer_plan: d_seq_offs out of order, a closing entry above bases_len, d_begin[r] < S[r],
+ * d_end[r] > S[r + 1], d_begin[r] > d_end[r].  No input makes a kernel read outside the caller's arrays and the table's words, or
+ * write outside [S[0], S[n_records]) of d_bases_out and the n_records entries of d_fixed.
+ * Not done: two errors within k of each other, indels, a repair chosen by count among several candidates, more than one pass (the
+ * caller can count again and call again), any pair rule, a new quality for a repaired base, masking instead of repairing. */
+typedef struct dsrcgpu_kmer_correct_rules
+{
+	uint64_t min_count;          /* >= 1: a window is SOLID iff it is good and the table's count of its key is >= min_count */
+	uint32_t max_quality;        /* 0 .. 255: a base above it is never replaced; 255 = any, and then in->d_quals is not read and may be NULL */
+	uint32_t reserved[5];        /* must be 0 */
+} dsrcgpu_kmer_correct_rules;
+
+int dsrcgpu_columns_kmer_correct(dsrcgpu_handle* h, const dsrcgpu_columns_in* in, const dsrcgpu_kmer_correct_rules* rules,
+		const uint64_t* d_table                        /* device: a table of dsrcgpu_columns_kmer_count, only read */,
+		const uint64_t* d_begin, const uint64_t* d_end, const uint8_t* d_keep            /* device, the plan, each may be NULL */,
+		uint8_t* d_bases_out                           /* device, addressed like in->d_bases; may be in->d_bases */,
+		uint64_t* d_fixed                              /* device, n_records, may be NULL */,
+		uint64_t stats[16]);
+
 /* Queue form of DsrcCompressor::Process (src/DsrcWorker.cpp:39-70):
  *   fastqQueue.Pop(partId, chunk)            -> dsrcgpu_submit(partId, chunk)      (bytes are copied into page-locked staging)
  *   ... Store ... dsrcQueue.Push(partId, blk) -> dsrcgpu_collect(&partId, &blk, ...)
