@@ -29,7 +29,7 @@ EXPORTS = [
     "dsrcgpu_columns_trim_plan", "dsrcgpu_columns_select_device", "dsrcgpu_columns_adapter_plan", "dsrcgpu_columns_pair_plan",
     "dsrcgpu_columns_profile", "dsrcgpu_columns_merge_device", "dsrcgpu_columns_dedup_plan",
     "dsrcgpu_columns_kmer_count", "dsrcgpu_kmer_table_merge", "dsrcgpu_kmer_spectrum", "dsrcgpu_kmer_lookup",
-    "dsrcgpu_columns_kmer_plan", "dsrcgpu_columns_kmer_correct",
+    "dsrcgpu_columns_kmer_plan", "dsrcgpu_columns_kmer_correct", "dsrcgpu_columns_complexity_plan",
 ]
 
 # error codes of include/dsrc_gpu.h that callers tell apart (DsrcGpuError.code)
@@ -99,6 +99,27 @@ class AdapterRules(C.Structure):
 
 ADAPTER_STATS = ("records_kept", "bases_kept", "bases_cut", "records_trimmed", "dropped_length") + tuple("found_%d" % a for a in range(8))
 NO_ADAPTER = 0xFFFFFFFF          # d_which of a record in which none was found
+
+
+class ComplexityRules(C.Structure):
+    """dsrcgpu_complexity_rules: the figures of dsrcgpu_columns_complexity_plan.  ComplexityRules(tail_bases, head_bases,
+    poly_min_length, poly_max_error_permille, min_length, min_complexity_permille, max_dust, max_dust_windows): the masks hold bit X
+    for base X (A = 1, C = 2, G = 4, T = 8), max_dust 0xFFFFFFFF = off; the library is the one that refuses figures out of range."""
+    _fields_ = [("tail_bases", C.c_uint32), ("head_bases", C.c_uint32), ("poly_min_length", C.c_uint32), ("poly_max_error_permille", C.c_uint32),
+                ("min_length", C.c_uint32), ("min_complexity_permille", C.c_uint32), ("max_dust", C.c_uint32), ("max_dust_windows", C.c_uint32),
+                ("reserved", C.c_uint32 * 4)]
+
+    def __init__(self, tail_bases=0, head_bases=0, poly_min_length=10, poly_max_error_permille=125, min_length=1, min_complexity_permille=0,
+                 max_dust=0xFFFFFFFF, max_dust_windows=0, reserved=(0, 0, 0, 0)):
+        super().__init__()
+        self.tail_bases, self.head_bases, self.poly_min_length, self.poly_max_error_permille = tail_bases, head_bases, poly_min_length, poly_max_error_permille
+        self.min_length, self.min_complexity_permille, self.max_dust, self.max_dust_windows = min_length, min_complexity_permille, max_dust, max_dust_windows
+        self.reserved = (C.c_uint32 * 4)(*reserved)
+
+
+COMPLEXITY_STATS = ("records_kept", "bases_kept", "bases_cut_5", "bases_cut_3", "records_head_cut", "records_tail_cut") + \
+    tuple("tail_" + x for x in "ACGT") + tuple("head_" + x for x in "ACGT") + ("dropped_length", "dropped_complexity", "dropped_dust")
+COMPLEXITY_NONE = 255            # DSRCGPU_COMPLEXITY_NONE: the head / tail base of a record without a cut at that end
 
 
 class PairRules(C.Structure):
@@ -577,6 +598,19 @@ class Handle:
         self._chk(self.L.dsrcgpu_columns_adapter_plan(self.h, C.byref(cols_in), C.byref(rules), C.c_void_p(d_begin_in), C.c_void_p(d_end_in),
                                                       C.c_void_p(d_keep_in), C.c_void_p(d_begin), C.c_void_p(d_end), C.c_void_p(d_keep),
                                                       C.c_void_p(d_which), stats))
+        return list(stats)
+
+    def columns_complexity_plan(self, cols_in: ColumnsIn, rules: ComplexityRules, d_begin_in, d_end_in, d_keep_in, d_begin: int, d_end: int,
+                                d_keep: int, d_info=None):
+        """dsrcgpu_columns_complexity_plan: poly-X ends, the complexity filter and the DUST filter on the plan d_begin_in / d_end_in /
+        d_keep_in (device addresses or None: whole reads, every record) into d_begin / d_end (uint64 each), d_keep (uint8) and, if
+        wanted, d_info (uint32, two per record: head base | tail base << 8, complexity permille | dust << 16), device memory of
+        n_records entries; an output may be the very array of its input.  Returns the twenty statistics (COMPLEXITY_STATS names the
+        first seventeen, the rest are 0)."""
+        stats = (C.c_uint64 * 20)()
+        self._chk(self.L.dsrcgpu_columns_complexity_plan(self.h, C.byref(cols_in), C.byref(rules), C.c_void_p(d_begin_in), C.c_void_p(d_end_in),
+                                                         C.c_void_p(d_keep_in), C.c_void_p(d_begin), C.c_void_p(d_end), C.c_void_p(d_keep),
+                                                         C.c_void_p(d_info), stats))
         return list(stats)
 
     def columns_pair_plan(self, cols_in1: ColumnsIn, cols_in2: ColumnsIn, rules: PairRules, plan1_in, plan2_in, d_begin1: int, d_end1: int,

@@ -265,6 +265,74 @@ def adapter_plan(handle: _lib.Handle, cols: RecordColumns, adapters, begin=None,
     return got + (which.to(torch.int64),) if return_which else got
 
 
+def _base_mask(name, bases):
+    """`bases` (a str over ACGT in either case, each base at most once) as the mask of dsrcgpu_complexity_rules: A = 1, C = 2, G = 4, T = 8."""
+    if not isinstance(bases, str) or any(ch not in _BASE_CODES for ch in bases.upper()) or len(set(bases.upper())) != len(bases):
+        raise ValueError("%s is a string over ACGT, each base at most once, %r given" % (name, bases))
+    return sum(1 << _BASE_CODES[ch] for ch in bases.upper())
+
+
+def _check_complexity_args(tail="", head="", poly_min_length=10, poly_max_error_permille=125, min_length=1, min_complexity_permille=0,
+                           max_dust=None, max_dust_windows=0):
+    """The keywords of complexity_plan, checked -> _lib.ComplexityRules.  ValueError for anything out of range."""
+    masks = _base_mask("tail", tail), _base_mask("head", head)
+    _check_int("poly_min_length", poly_min_length, 1, 0xFFFFFFFF)
+    _check_int("poly_max_error_permille", poly_max_error_permille, 0, 1000)
+    _check_int("min_length", min_length, 0, 0xFFFFFFFF)
+    _check_int("min_complexity_permille", min_complexity_permille, 0, 1000)
+    if max_dust is not None:
+        _check_int("max_dust", max_dust, 0, 0xFFFFFFFE)
+    _check_int("max_dust_windows", max_dust_windows, 0, 0xFFFFFFFF)
+    return _lib.ComplexityRules(masks[0], masks[1], poly_min_length, poly_max_error_permille, min_length, min_complexity_permille,
+                                0xFFFFFFFF if max_dust is None else max_dust, max_dust_windows)
+
+
+def _check_complexity(complexity):
+    if not isinstance(complexity, dict):
+        raise ValueError("complexity is a dict of complexity_plan keywords")
+    try:
+        _check_complexity_args(**complexity)
+    except TypeError:
+        raise ValueError("complexity holds keywords of complexity_plan (tail, head, poly_min_length, poly_max_error_permille, min_length, "
+                         "min_complexity_permille, max_dust, max_dust_windows), %r given" % sorted(complexity)) from None
+
+
+def complexity_plan(handle: _lib.Handle, cols: RecordColumns, begin=None, end=None, keep=None, tail: str = "", head: str = "",
+                    poly_min_length: int = 10, poly_max_error_permille: int = 125, min_length: int = 1, min_complexity_permille: int = 0,
+                    max_dust=None, max_dust_windows: int = 0, return_info: bool = False):
+    """dsrcgpu_columns_complexity_plan on the records of `cols`: poly-X runs are cut off the ends of the plan begin / end / keep (None:
+    whole reads, every record; as trim_plan returns them), then what is left is judged -> (begin, end, keep, stats[, head_base,
+    tail_base, complexity_permille, dust]) in fresh tensors.  tail / head: the bases (a str over ACGT) whose runs are searched at the
+    3' / 5' end -- fastp's poly-G is tail="G", its poly-X tail="ACGT", RNA-seq poly-A tails tail="A" and head="T"; a run is scored
+    +1 per position that holds the base and -2 per other one (cutadapt's poly-A rule), may hold poly_max_error_permille other
+    positions per 1000 and is cut if it spans at least poly_min_length.  A record is kept iff it came in kept, at least min_length
+    bases are left, at least min_complexity_permille of 1000 neighbouring positions of the rest differ (fastp's 30 % is 300; 0 = off)
+    and at most max_dust_windows of its 64-base windows score above max_dust (sdust's 20; None = off).  stats is a dict with the keys
+    of _lib.COMPLEXITY_STATS; head_base / tail_base (int64) are the base code cut at that end, -1 for none, complexity_permille and dust
+    (int64) the two scores of what is left; all four are -1 for a record that came in dropped.  Arguments out of range raise ValueError
+    before the library is called.  Nothing of the payload crosses to the host."""
+    rules = _check_complexity_args(tail, head, poly_min_length, poly_max_error_permille, min_length, min_complexity_permille, max_dust,
+                                   max_dust_windows)
+    device = cols.bases.device
+    R = cols.n_records
+    plan, plan_held = _stage_plan(R, device, [(begin, end)], keep)
+    cin, held = _columns_in(cols, titles=False)
+    out_begin = torch.empty(R, dtype=torch.int64, device=device); out_end = torch.empty(R, dtype=torch.int64, device=device)
+    out_keep = torch.empty(R, dtype=torch.uint8, device=device)
+    info = torch.empty((R, 2), dtype=torch.int32, device=device) if return_info else None
+    _quiesce(device)
+    stats = handle.columns_complexity_plan(cin, rules, *plan, out_begin.data_ptr(), out_end.data_ptr(), out_keep.data_ptr(), _adr(info))
+    del held, plan_held
+    got = (out_begin, out_end, out_keep, dict(zip(_lib.COMPLEXITY_STATS, stats)))
+    if not return_info:
+        return got
+    word0, word1 = info[:, 0].to(torch.int64), info[:, 1].to(torch.int64)
+    dropped = word0 == 0xFFFF
+    base = lambda v: torch.where(v == _lib.COMPLEXITY_NONE, torch.full_like(v, -1), v)
+    score = lambda v: torch.where(dropped, torch.full_like(v, -1), v)
+    return got + (base(word0 & 255), base((word0 >> 8) & 255), score(word1 & 0xFFFF), score((word1 >> 16) & 0xFFFF))
+
+
 @dataclasses.dataclass
 class ColumnsProfile:
     """A profile of dsrcgpu_columns_profile: one int64 tensor of _lib.profile_words(n_cycles) counts on the device of the columns
@@ -339,7 +407,7 @@ def profile_columns(handle: _lib.Handle, cols: RecordColumns, begin=None, end=No
 
 def filter_columns(handle: _lib.Handle, cols: RecordColumns, titles: bool = True, adapters=None, adapter_min_overlap: int = 3,
                    adapter_max_error_permille: int = 100, profile: bool = False, dedup: bool = False, dedup_key_bases: int = 0,
-                   dedup_prefer: str = "first", kmers=None, screen=None, correct=None, **rules):
+                   dedup_prefer: str = "first", kmers=None, screen=None, correct=None, complexity=None, **rules):
     """trim_plan(**rules) and select_columns with its plan in sequence: -> (RecordColumns of the trimmed, kept records, stats).
     adapters (see adapter_plan): between the two, adapter_plan narrows the trim plan -- the quality trim first, the adapter second,
     the order of cutadapt and fastp -- with the same min_length; stats is then the trim plan's dict plus a key "adapter" that holds
@@ -359,9 +427,14 @@ def filter_columns(handle: _lib.Handle, cols: RecordColumns, titles: bool = True
     in front of the screen, correct_kmers repairs the bases on the ranges and keep at that point -- with k= against the table of
     count_kmers(k) of the batch under that very plan; stats gets "correct", its dict.  Everything behind it (screen, dedup,
     "profile_after", "kmers_after", the select) sees the repaired bases; `cols` stays as it is, and "profile_before", and max_n of
-    the trim plan, saw the bases as they came."""
+    the trim plan, saw the bases as they came.
+    complexity (a dict of complexity_plan keywords): behind the adapter plan and in front of correct, complexity_plan cuts poly-X ends
+    and drops low-complexity reads, with the filter's min_length unless the dict gives one; stats gets "complexity", its dict, and
+    everything behind it sees the narrowed plan."""
     if adapters is not None:
         codes = _adapter_codes(adapters)
+    if complexity is not None:
+        _check_complexity(complexity)
     if screen is not None:
         _check_screen(screen, cols)
     if correct is not None:
@@ -375,6 +448,9 @@ def filter_columns(handle: _lib.Handle, cols: RecordColumns, titles: bool = True
         begin, end, keep, a_stats = adapter_plan(handle, cols, codes, begin, end, keep, adapter_min_overlap, adapter_max_error_permille,
                                                  rules.get("min_length", 1))
         stats = dict(stats, adapter=a_stats)
+    if complexity is not None:
+        begin, end, keep, x_stats = complexity_plan(handle, cols, begin, end, keep, **dict(dict(min_length=rules.get("min_length", 1)), **complexity))
+        stats = dict(stats, complexity=x_stats)
     came = cols
     if correct is not None:
         cols, c_stats = _correct_step(handle, [(cols, begin, end, keep)], correct)[0]
@@ -553,7 +629,7 @@ def filter_pairs(handle: _lib.Handle, cols1: RecordColumns, cols2: RecordColumns
                  overlap: bool = True, pair_min_overlap: int = 30, pair_max_mismatches: int = 5, pair_max_error_permille: int = 200,
                  adapter_min_overlap: int = 3, adapter_max_error_permille: int = 100, profile: bool = False, merge: bool = False,
                  merge_quality_cap: int = 41, dedup: bool = False, dedup_key_bases: int = 0, dedup_prefer: str = "first", kmers=None, screen=None,
-                 correct=None, **rules):
+                 correct=None, complexity=None, **rules):
     """filter_columns for paired-end data: per side trim_plan(**rules) and, if adapters<s> is given, adapter_plan; then pair_plan with
     the same min_length, which cuts read-through found from the overlap of the mates and decides per PAIR; then one select_columns per
     side with that side's ranges and the joint keep -> (out1, out2, stats), out1.n_records == out2.n_records always and record j of
@@ -578,7 +654,11 @@ def filter_pairs(handle: _lib.Handle, cols1: RecordColumns, cols2: RecordColumns
     stats["read1"]["screen"] and stats["read2"]["screen"] are its dicts.
     correct (as in filter_columns): per side, behind that side's adapter plan and in front of the screen and the pair plan, correct_kmers
     repairs the bases; with k= ONE table of both mates under their plans is counted first.  stats["read1"]["correct"] and
-    stats["read2"]["correct"] are its dicts; everything behind it sees the repaired bases, "profile_before" the bases as they came."""
+    stats["read2"]["correct"] are its dicts; everything behind it sees the repaired bases, "profile_before" the bases as they came.
+    complexity (as in filter_columns): per side, behind that side's adapter plan and in front of correct, the screen and the pair plan --
+    poly-G tails spoil the overlap search; stats["read1"]["complexity"] and stats["read2"]["complexity"] are its dicts."""
+    if complexity is not None:
+        _check_complexity(complexity)
     if dedup:
         _check_dedup_args(dedup_key_bases, dedup_prefer)
     if correct is not None:
@@ -600,6 +680,10 @@ def filter_pairs(handle: _lib.Handle, cols1: RecordColumns, cols2: RecordColumns
             begin, end, keep, a_stats = adapter_plan(handle, cols, codes, begin, end, keep, adapter_min_overlap, adapter_max_error_permille,
                                                      rules.get("min_length", 1))
             side = dict(side, adapter=a_stats)
+        if complexity is not None:
+            begin, end, keep, x_stats = complexity_plan(handle, cols, begin, end, keep,
+                                                        **dict(dict(min_length=rules.get("min_length", 1)), **complexity))
+            side = dict(side, complexity=x_stats)
         plans.append((begin, end, keep)); stats[name] = side
     came1, came2 = cols1, cols2
     if correct is not None:

@@ -55,6 +55,7 @@
 #include "k_columns_kmer.h"
 #include "k_columns_kmer_plan.h"
 #include "k_columns_kmer_correct.h"
+#include "k_columns_complexity.h"
 
 namespace
 {

@@ -394,6 +394,41 @@ int dsrcgpu_columns_adapter_plan(dsrcgpu_handle* h, const dsrcgpu_columns_in* in
 	return DSRCGPU_OK;
 }
 
+// the complexity plan (k_columns_complexity.h): the rules are checked here, then the check pass of the adapter plan and the planner
+// run back to back as in dsrcgpu_columns_adapter_plan
+int dsrcgpu_columns_complexity_plan(dsrcgpu_handle* h, const dsrcgpu_columns_in* in, const dsrcgpu_complexity_rules* rules,
+									const uint64_t* d_begin_in, const uint64_t* d_end_in, const uint8_t* d_keep_in,
+									uint64_t* d_begin, uint64_t* d_end, uint8_t* d_keep, uint32_t* d_info, uint64_t stats[20])
+{
+	if (!h) return DSRCGPU_E_ARG;
+	if (!rules || !stats) return fail(h, DSRCGPU_E_ARG, "null argument");
+	for (u32 k = 0; k < CPLX_STATS; ++k) stats[k] = 0;
+	ColIn c;
+	if (const int rc = col_in_args(h, in, 0, c)) return rc;
+	if (rules->tail_bases > 15) return fail(h, DSRCGPU_E_ARG, "complexity rules: tail_bases above 15 (A = 1, C = 2, G = 4, T = 8)");
+	if (rules->head_bases > 15) return fail(h, DSRCGPU_E_ARG, "complexity rules: head_bases above 15 (A = 1, C = 2, G = 4, T = 8)");
+	if ((rules->tail_bases | rules->head_bases) && rules->poly_min_length == 0) return fail(h, DSRCGPU_E_ARG, "complexity rules: poly_min_length of 0 with a base to search");
+	if (rules->poly_max_error_permille > 1000) return fail(h, DSRCGPU_E_ARG, "complexity rules: poly_max_error_permille above 1000");
+	if (rules->min_complexity_permille > 1000) return fail(h, DSRCGPU_E_ARG, "complexity rules: min_complexity_permille above 1000");
+	if (const int rc = reserved_clear(h, "complexity rules", rules->reserved)) return rc;
+	if (const int rc = together(h, d_begin_in, d_end_in, "d_begin_in", "d_end_in")) return rc;
+	if (c.n_recs == 0) return DSRCGPU_OK;
+	if (!d_begin || !d_end || !d_keep) return fail(h, DSRCGPU_E_ARG, "null argument");
+	HIPCHK(hipSetDevice(h->device));
+	hipStream_t s = h->stream;
+	if (const int rc = ensure_arena(h, (CPLX_STATS + 1) * 8 + 1024)) return rc;
+	ResWords res = res_alloc(h, 1, CPLX_STATS);           // error word, the twenty statistics
+	if (const int rc = res_begin(h, res, "complexity plan")) return rc;
+	const AdaptPlanIn w{d_begin_in, d_end_in, d_keep_in};
+	const CplxRules R{rules->tail_bases, rules->head_bases, rules->poly_min_length, rules->poly_max_error_permille, rules->min_length,
+	                  rules->min_complexity_permille, rules->max_dust, rules->max_dust_windows};
+	hipLaunchKernelGGL(k_adapt_check, grid_threads(c.n_recs), dim3(WG), 0, s, c, w, res.d); KCHK();
+	hipLaunchKernelGGL(k_cplx_plan, grid_waves(c.n_recs), dim3(WG), 0, s, c, w, R, d_begin, d_end, d_keep, d_info, res.counters(), res.d); KCHK();
+	if (const int rc = res_home(h, res)) return rc;
+	for (u32 k = 0; k < CPLX_STATS; ++k) stats[k] = res.home()[k];
+	return DSRCGPU_OK;
+}
+
 // the pair plan (k_columns_pair.h): the check pass of the adapter plan once per side, each with an error word of its own (side 1 is
 // reported first), then the planner; the error words and the statistics come home in one copy
 int dsrcgpu_columns_pair_plan(dsrcgpu_handle* h, const dsrcgpu_columns_in* in1, const dsrcgpu_columns_in* in2, const dsrcgpu_pair_rules* rules,

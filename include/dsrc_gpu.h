@@ -269,8 +269,8 @@ int dsrcgpu_columns_select_device(dsrcgpu_handle* h, const dsrcgpu_columns_in* i
  * the record came in kept and d_end[r] - d_begin[r] >= min_length, else 0.  A record that came in dropped is not searched: its range
  * passes through, d_keep[r] = 0, d_which[r] = 0xFFFFFFFF, and it counts in no statistic.  Positions at or beyond e are outside the read
  * whatever the array holds there (the next record, or a tail an earlier plan has cut).  d_which may be NULL.
- * Not done here: indels, 5' and anchored adapters, IUPAC wildcards in the adapter, "best match" instead of leftmost, poly-G tails.
- * (Paired-end overlap detection: dsrcgpu_columns_pair_plan, below.)
+ * Not done here: indels, 5' and anchored adapters, IUPAC wildcards in the adapter, "best match" instead of leftmost.
+ * (Poly-G tails and other poly-X ends: dsrcgpu_columns_complexity_plan.  Paired-end overlap detection: dsrcgpu_columns_pair_plan.  Both below.)
  * stats (host): [0] records kept, [1] bases kept, [2] bases this call cut off kept records, [3] records in which an adapter was found
  * (among those that came in kept), [4] records dropped for length, [5 + a] records in which adapter a was the one found.
  * n_records == 0: DSRCGPU_OK, stats 0.
@@ -298,6 +298,69 @@ int dsrcgpu_columns_adapter_plan(dsrcgpu_handle* h, const dsrcgpu_columns_in* in
 		uint64_t* d_begin, uint64_t* d_end, uint8_t* d_keep                              /* device, n_records each */,
 		uint32_t* d_which                                                                /* device, n_records, may be NULL */,
 		uint64_t stats[13]);
+
+/* dsrcgpu_columns_complexity_plan: the sixth planner -- poly-X runs are cut off either end of the range (the poly-G tails of two-colour
+ * instruments, poly-A / poly-T of RNA-seq), then what is left is judged for length, for complexity (fastp's measure) and for a windowed
+ * DUST score.  Plan in, plan out, for dsrcgpu_columns_select_device to carry out.  Conventions as dsrcgpu_columns_adapter_plan: the
+ * handle's own lane and stream, scratch from the arena, synchronised before it returns, codec state left alone, a colour-space handle:
+ * DSRCGPU_E_ARG.  Of `in` only d_bases and d_seq_offs are read.  The plan in: d_begin_in / d_end_in (both NULL = whole reads, one
+ * without the other: DSRCGPU_E_ARG) and d_keep_in (NULL = every record; any non-zero byte keeps).
+ * For record r that came in kept, with b = d_begin_in[r], e = d_end_in[r], n = e - b, x[i] = d_bases[b + i]:
+ * The 3' run of base X, for every X in tail_bases (the whole range is walked, there is no early break in the rule):
+ *   best = 0, cut = n, m = 0, err = 0
+ *   for i = n - 1 down to 0:
+ *     if x[i] == X: m += 1  else: err += 1                       (a code >= 4 -- N .. 255 -- is never X)
+ *     L = n - i;  score = m - 2 * err                            (signed; cutadapt's poly-A score with the error share a parameter)
+ *     if score > best and err * 1000 <= L * poly_max_error_permille:  best = score, cut = i
+ *   t_X = n - cut;  if t_X < poly_min_length: t_X = 0
+ * Strict > : the shortest run that reaches the highest score wins.  t = the largest t_X (two bases cannot tie above 0: x[n - t] holds one
+ * of them), the tail base is that X, DSRCGPU_COMPLEXITY_NONE if t = 0.  The 5' run is the mirror image for every X in head_bases (i from
+ * 0 up, L = i + 1, cut = i + 1) and gives hd and the head base.  Each end is searched by itself on the range as it came.  If hd + t >= n
+ * the range is empty, d_begin[r] = d_end[r] = b; otherwise d_begin[r] = b + hd, d_end[r] = e - t.  x', n' are what is left.
+ * Complexity: d = the number of i < n' - 1 with x'[i] != x'[i + 1] (codes as they are: N equals N); cp = n' >= 2 ? floor(d * 1000 /
+ * (n' - 1)) : 1000; the record fails iff n' >= 2 and d * 1000 < min_complexity_permille * (n' - 1).
+ * DUST, windowed so that it does not grow with the read: windows of 64 positions start at 0, 32, 64, .. up to and including n' - 64, one
+ * more at n' - 64 if that is no multiple of 32; n' < 64: the one window [0, n').  In a window [s, s + w) a triplet starts at i = s ..
+ * s + w - 3 and is valid iff x'[i], x'[i + 1], x'[i + 2] are all < 4; its code is 16 x'[i] + 4 x'[i + 1] + x'[i + 2].  With c_t the count
+ * of code t, l = sum c_t, S = sum c_t (c_t - 1) / 2:  v = l >= 2 ? floor(10 * S / (l - 1)) : 0  (at most 310).  The record fails iff more
+ * than max_dust_windows windows have v > max_dust; dust = the largest v of the record.
+ * d_keep[r] = 1 iff, in this order (the first rule that fails is the one counted): n' >= min_length, complexity, DUST.  Both filters judge
+ * the range AFTER the cuts.  d_info (may be NULL): d_info[2r] = head base | tail base << 8, d_info[2r + 1] = cp | dust << 16, for every
+ * record that came in kept, whichever filters are on.  A record that came in dropped is not examined: its range passes through,
+ * d_keep[r] = 0, d_info = {0xFFFF, 0}, and it counts in no statistic.  Positions outside [b, e) are outside the read whatever the array
+ * holds there.
+ * Not done here: a quality-aware poly rule, masking of low-complexity stretches inside a read, an entropy score, weighted windows
+ * (prinseq's mean over windows), a sliding-window quality cut.
+ * stats (host): [0] records kept, [1] bases kept, [2] / [3] bases cut off the 5' / 3' ends of kept records (d_begin[r] - b and e -
+ * d_end[r], so that [1] + [2] + [3] is what the kept records came with), [4] / [5] records with a head / tail cut among those that came
+ * in kept, [6..9] tail cuts by base A C G T, [10..13] head cuts by base A C G T, [14] records dropped for length, [15] for complexity,
+ * [16] for DUST, [17..19] 0.
+ * n_records == 0: DSRCGPU_OK, stats 0.
+ * DSRCGPU_E_ARG, nothing written: tail_bases or head_bases above 15; poly_min_length 0 with a base to search; poly_max_error_permille or
+ * min_complexity_permille above 1000; a non-zero reserved field; a half-given range pair.  No base to search and both filters off is
+ * legal: a pure length filter.
+ * DSRCGPU_E_INPUT (lowest record and reason in dsrcgpu_last_error, outputs untouched), for kept and dropped records alike: the
+ * conditions of dsrcgpu_columns_adapter_plan.  No input makes a kernel read outside the caller's arrays.
+ * In place: as dsrcgpu_columns_adapter_plan (d_begin == d_begin_in, d_end == d_end_in, d_keep == d_keep_in). */
+#define DSRCGPU_COMPLEXITY_NONE 255u
+typedef struct dsrcgpu_complexity_rules
+{
+	uint32_t tail_bases;               /* bit X (A = 1, C = 2, G = 4, T = 8): a 3' run of base X is searched; 0: the 3' end is left alone; > 15: DSRCGPU_E_ARG */
+	uint32_t head_bases;               /* the same for the 5' end */
+	uint32_t poly_min_length;          /* a run is cut only if it spans at least this many positions; 0 with a mask set: DSRCGPU_E_ARG */
+	uint32_t poly_max_error_permille;  /* 0..1000: positions of the run that may hold something else, per 1000 */
+	uint32_t min_length;               /* keep a record iff this many bases are left */
+	uint32_t min_complexity_permille;  /* 0 = off, ..1000 */
+	uint32_t max_dust;                 /* 0xFFFFFFFF = off */
+	uint32_t max_dust_windows;         /* a record may have this many windows above max_dust */
+	uint32_t reserved[4];              /* must be 0, else DSRCGPU_E_ARG */
+} dsrcgpu_complexity_rules;
+
+int dsrcgpu_columns_complexity_plan(dsrcgpu_handle* h, const dsrcgpu_columns_in* in, const dsrcgpu_complexity_rules* rules,
+		const uint64_t* d_begin_in, const uint64_t* d_end_in, const uint8_t* d_keep_in   /* device, may be NULL */,
+		uint64_t* d_begin, uint64_t* d_end, uint8_t* d_keep                              /* device, n_records each */,
+		uint32_t* d_info                                                                 /* device, 2 per record, may be NULL */,
+		uint64_t stats[20]);
 
 /* dsrcgpu_columns_pair_plan: the third planner, for paired-end data -- two column sets of equally many records, record r of `in2` is
  * the mate of record r of `in1`.  It takes a plan in per side and gives a narrower plan out per side and ONE keep flag per pair, so
