@@ -44,6 +44,7 @@
 #include "k_dec_rc.h"
 #include "k_dec_tags.h"
 #include "k_dec_q0.h"
+#include "k_columns_common.h"
 #include "k_columns.h"
 #include "k_columns_enc.h"
 #include "k_columns_sel.h"

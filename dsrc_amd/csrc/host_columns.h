@@ -386,8 +386,8 @@ int dsrcgpu_columns_adapter_plan(dsrcgpu_handle* h, const dsrcgpu_columns_in* in
 	if (const int rc = ensure_arena(h, 14 * 8 + 1024)) return rc;
 	ResWords res = res_alloc(h, 1, 13);                   // error word, the thirteen statistics
 	if (const int rc = res_begin(h, res, "adapter plan")) return rc;
-	const AdaptPlanIn w{d_begin_in, d_end_in, d_keep_in};
-	hipLaunchKernelGGL(k_adapt_check, grid_threads(c.n_recs), dim3(WG), 0, s, c, w, res.d); KCHK();
+	const ColPlanIn w{d_begin_in, d_end_in, d_keep_in};
+	hipLaunchKernelGGL(k_col_plan_check, grid_threads(c.n_recs), dim3(WG), 0, s, c, w, res.d); KCHK();
 	hipLaunchKernelGGL(k_adapt_plan, grid_waves(c.n_recs), dim3(WG), 0, s, c, w, R, d_begin, d_end, d_keep, d_which, res.counters(), res.d); KCHK();
 	if (const int rc = res_home(h, res)) return rc;
 	for (u32 k = 0; k < 13; ++k) stats[k] = res.home()[k];
@@ -419,10 +419,10 @@ int dsrcgpu_columns_complexity_plan(dsrcgpu_handle* h, const dsrcgpu_columns_in*
 	if (const int rc = ensure_arena(h, (CPLX_STATS + 1) * 8 + 1024)) return rc;
 	ResWords res = res_alloc(h, 1, CPLX_STATS);           // error word, the twenty statistics
 	if (const int rc = res_begin(h, res, "complexity plan")) return rc;
-	const AdaptPlanIn w{d_begin_in, d_end_in, d_keep_in};
+	const ColPlanIn w{d_begin_in, d_end_in, d_keep_in};
 	const CplxRules R{rules->tail_bases, rules->head_bases, rules->poly_min_length, rules->poly_max_error_permille, rules->min_length,
 	                  rules->min_complexity_permille, rules->max_dust, rules->max_dust_windows};
-	hipLaunchKernelGGL(k_adapt_check, grid_threads(c.n_recs), dim3(WG), 0, s, c, w, res.d); KCHK();
+	hipLaunchKernelGGL(k_col_plan_check, grid_threads(c.n_recs), dim3(WG), 0, s, c, w, res.d); KCHK();
 	hipLaunchKernelGGL(k_cplx_plan, grid_waves(c.n_recs), dim3(WG), 0, s, c, w, R, d_begin, d_end, d_keep, d_info, res.counters(), res.d); KCHK();
 	if (const int rc = res_home(h, res)) return rc;
 	for (u32 k = 0; k < CPLX_STATS; ++k) stats[k] = res.home()[k];
@@ -456,11 +456,11 @@ int dsrcgpu_columns_pair_plan(dsrcgpu_handle* h, const dsrcgpu_columns_in* in1, 
 	if (const int rc = ensure_arena(h, (2 + PAIR_N_STATS) * 8 + 1024)) return rc;
 	ResWords res = res_alloc(h, 2, PAIR_N_STATS);         // an error word per side, the eleven statistics
 	if (const int rc = res_begin(h, res, "pair plan")) return rc;
-	const AdaptPlanIn w1{d_begin1_in, d_end1_in, d_keep1_in}, w2{d_begin2_in, d_end2_in, d_keep2_in};
+	const ColPlanIn w1{d_begin1_in, d_end1_in, d_keep1_in}, w2{d_begin2_in, d_end2_in, d_keep2_in};
 	const PairRules R{rules->min_overlap, rules->max_mismatches, rules->max_error_permille, rules->min_length};
 	const PairOut o{d_begin1, d_end1, d_begin2, d_end2, d_keep, d_insert};
-	hipLaunchKernelGGL(k_adapt_check, grid_threads(c1.n_recs), dim3(WG), 0, s, c1, w1, res.d); KCHK();
-	hipLaunchKernelGGL(k_adapt_check, grid_threads(c1.n_recs), dim3(WG), 0, s, c2, w2, res.d + 1); KCHK();
+	hipLaunchKernelGGL(k_col_plan_check, grid_threads(c1.n_recs), dim3(WG), 0, s, c1, w1, res.d); KCHK();
+	hipLaunchKernelGGL(k_col_plan_check, grid_threads(c1.n_recs), dim3(WG), 0, s, c2, w2, res.d + 1); KCHK();
 	hipLaunchKernelGGL(k_pair_plan, grid_waves(c1.n_recs), dim3(WG), 0, s, c1, c2, w1, w2, R, o, res.counters(), res.d); KCHK();
 	if (const int rc = res_home(h, res, "pair plan")) return rc;
 	for (u32 k = 0; k < PAIR_N_STATS; ++k) stats[k] = res.home()[k];
@@ -509,12 +509,12 @@ int dsrcgpu_columns_dedup_plan(dsrcgpu_handle* h, const dsrcgpu_columns_in* in1,
 	HIPCHK(hipMemsetAsync(t.best, 0, (size_t)M * 8, s));
 	HIPCHK(hipMemsetAsync(t.count, 0, (size_t)M * 4, s));
 	if (quals) HIPCHK(hipMemsetAsync(t.low, 0xFF, (size_t)M * 4, s));
-	const AdaptPlanIn w1{d_begin1, d_end1, nullptr}, w2{d_begin2, d_end2, nullptr};
+	const ColPlanIn w1{d_begin1, d_end1, nullptr}, w2{d_begin2, d_end2, nullptr};
 	const u32 bits = rules->hash_bits;
 	const DedupIn in{c1, c2, w1, w2, d_keep_in, rules->key_bases, bits == 0 || bits == 64 ? ~0ull : (1ull << bits) - 1ull, two ? 1u : 0u, rules->prefer};
 	const dim3 g_check = grid_threads(R), g_wave = grid_waves(R);
-	hipLaunchKernelGGL(k_adapt_check, g_check, dim3(WG), 0, s, c1, w1, res.d); KCHK();
-	if (two) { hipLaunchKernelGGL(k_adapt_check, g_check, dim3(WG), 0, s, c2, w2, res.d + 1); KCHK(); }
+	hipLaunchKernelGGL(k_col_plan_check, g_check, dim3(WG), 0, s, c1, w1, res.d); KCHK();
+	if (two) { hipLaunchKernelGGL(k_col_plan_check, g_check, dim3(WG), 0, s, c2, w2, res.d + 1); KCHK(); }
 	hipLaunchKernelGGL(k_dedup_key, g_wave, dim3(WG), 0, s, in, AP<u64>(h, o_hash), AP<u64>(h, o_rank), res.counters(), res.d); KCHK();
 	hipLaunchKernelGGL(k_dedup_insert, g_wave, dim3(WG), 0, s, in, AP<u64>(h, o_hash), AP<u64>(h, o_rank), t, AP<u32>(h, o_slot), res.d); KCHK();
 	hipLaunchKernelGGL(k_dedup_resolve, g_check, dim3(WG), 0, s, d_keep_in, R, t, AP<u32>(h, o_slot), rules->prefer, d_keep, d_dup_of, d_copies, res.counters(), res.d); KCHK();
@@ -564,12 +564,12 @@ int dsrcgpu_columns_merge_device(dsrcgpu_handle* h, const dsrcgpu_columns_in* in
 	u64* d_pos = AP<u64>(h, h->arena.alloc((size_t)c1.n_recs * 8));
 	if (const int rc = res_begin(h, res, "columns merge")) return rc;
 	HIPCHK(hipMemsetAsync(d_len, 0xFF, (size_t)c1.n_recs * 8, s));      // MERGE_NOT: a pair the judge does not reach is not merged
-	const MergeWhat w{AdaptPlanIn{d_begin1, d_end1, nullptr}, AdaptPlanIn{d_begin2, d_end2, nullptr}, d_keep, d_insert};
+	const MergeWhat w{ColPlanIn{d_begin1, d_end1, nullptr}, ColPlanIn{d_begin2, d_end2, nullptr}, d_keep, d_insert};
 	const MergeRules R{rules->min_overlap, rules->max_mismatches, rules->max_error_permille, rules->quality_cap};
 	const dim3 g_check = grid_threads(c1.n_recs), g_waves = grid_waves(c1.n_recs);
 	const u32 g_tiles = (u32)std::min<u64>(4096, n_tiles);
-	hipLaunchKernelGGL(k_adapt_check, g_check, dim3(WG), 0, s, c1, w.w1, res.d); KCHK();
-	hipLaunchKernelGGL(k_adapt_check, g_check, dim3(WG), 0, s, c2, w.w2, res.d + 1); KCHK();
+	hipLaunchKernelGGL(k_col_plan_check, g_check, dim3(WG), 0, s, c1, w.w1, res.d); KCHK();
+	hipLaunchKernelGGL(k_col_plan_check, g_check, dim3(WG), 0, s, c2, w.w2, res.d + 1); KCHK();
 	hipLaunchKernelGGL(k_merge_judge, g_waves, dim3(WG), 0, s, c1, c2, w, R, d_len, res.counters(), res.d); KCHK();
 	hipLaunchKernelGGL(k_merge_tiles, dim3(g_tiles), dim3(WG), 0, s, c1, d_len, titles ? 1u : 0u, n_tiles, d_tiles, res.d); KCHK();
 	hipLaunchKernelGGL(k_sel_scan_tiles, dim3(1), dim3(WG), 0, s, n_tiles, d_tiles, res.counters() + MERGE_N_STATS); KCHK();
@@ -613,9 +613,9 @@ int dsrcgpu_columns_profile(dsrcgpu_handle* h, const dsrcgpu_columns_in* in, con
 	if (const int rc = ensure_arena(h, (size_t)(words + 1) * 8 + 1024)) return rc;
 	ResWords res = res_alloc(h, 1, words);                // error word, this call's profile
 	if (const int rc = res_begin(h, res, "columns profile")) return rc;
-	const AdaptPlanIn w{d_begin, d_end, d_keep};
+	const ColPlanIn w{d_begin, d_end, d_keep};
 	const dim3 grid = grid_waves(c.n_recs, prof_max_grid(C));
-	hipLaunchKernelGGL(k_adapt_check, grid_threads(c.n_recs), dim3(WG), 0, s, c, w, res.d); KCHK();
+	hipLaunchKernelGGL(k_col_plan_check, grid_threads(c.n_recs), dim3(WG), 0, s, c, w, res.d); KCHK();
 	if (C <= PROF_SMALL_CYCLES) { hipLaunchKernelGGL(k_prof<PROF_SMALL_CYCLES>, grid, dim3(WG), 0, s, c, w, C, res.counters(), res.d); KCHK(); }
 	else { hipLaunchKernelGGL(k_prof<PROF_MAX_CYCLES>, grid, dim3(WG), 0, s, c, w, C, res.counters(), res.d); KCHK(); }
 	hipLaunchKernelGGL(k_prof_store, dim3((words + WG - 1) / WG), dim3(WG), 0, s, res.counters(), d_profile, words, rules->accumulate, res.d); KCHK();
@@ -674,8 +674,8 @@ int dsrcgpu_columns_kmer_count(dsrcgpu_handle* h, const dsrcgpu_columns_in* in, 
 	ResWords res = res_alloc(h, 1, KMER_N_STATS);         // the error word, the sixteen statistics
 	if (const int rc = res_begin(h, res, "kmer count")) return rc;
 	u64* const st = res.counters();
-	const AdaptPlanIn w{d_begin, d_end, d_keep};
-	hipLaunchKernelGGL(k_adapt_check, grid_threads(c.n_recs), dim3(WG), 0, s, c, w, res.d); KCHK();
+	const ColPlanIn w{d_begin, d_end, d_keep};
+	hipLaunchKernelGGL(k_col_plan_check, grid_threads(c.n_recs), dim3(WG), 0, s, c, w, res.d); KCHK();
 	hipLaunchKernelGGL(k_kmer_windows, grid_threads(c.n_recs), dim3(WG), 0, s, c, w, k, st, res.d); KCHK();
 	if (const int rc = res_home(h, res)) return rc;
 	const u64 W = res.home()[KMER_WINDOWS];
@@ -810,10 +810,10 @@ int dsrcgpu_columns_kmer_plan(dsrcgpu_handle* h, const dsrcgpu_columns_in* in, c
 	if (const int rc = ensure_arena(h, res_bytes + 1024)) return rc;
 	ResWords res = res_alloc(h, 1, KPLAN_N_STATS + 1);
 	if (const int rc = res_begin(h, res, "kmer plan")) return rc;
-	const AdaptPlanIn w{d_begin_in, d_end_in, d_keep_in};
+	const ColPlanIn w{d_begin_in, d_end_in, d_keep_in};
 	const u64 wpg = WG / 64;
 	u64 gx = grid_waves(c.n_recs).x;
-	hipLaunchKernelGGL(k_adapt_check, grid_threads(c.n_recs), dim3(WG), 0, s, c, w, res.d); KCHK();
+	hipLaunchKernelGGL(k_col_plan_check, grid_threads(c.n_recs), dim3(WG), 0, s, c, w, res.d); KCHK();
 	u16* d_spill = nullptr;
 	u64 stride = 0;
 	if (median)
@@ -867,9 +867,9 @@ int dsrcgpu_columns_kmer_correct(dsrcgpu_handle* h, const dsrcgpu_columns_in* in
 	if (const int rc = ensure_arena(h, (1 + KCORR_N_STATS) * 8 + 1024)) return rc;
 	ResWords res = res_alloc(h, 1, KCORR_N_STATS);        // the error word, the sixteen statistics
 	if (const int rc = res_begin(h, res, "kmer correct")) return rc;
-	const AdaptPlanIn w{d_begin, d_end, d_keep};
+	const ColPlanIn w{d_begin, d_end, d_keep};
 	const KmerCorrectRules R{rules->min_count, rules->max_quality};
-	hipLaunchKernelGGL(k_adapt_check, grid_threads(c.n_recs), dim3(WG), 0, s, c, w, res.d); KCHK();
+	hipLaunchKernelGGL(k_col_plan_check, grid_threads(c.n_recs), dim3(WG), 0, s, c, w, res.d); KCHK();
 	if (d_bases_out != c.bases) { hipLaunchKernelGGL(k_kmer_correct_copy, grid_threads(c.bases_len / 8 + 1, 4096), dim3(WG), 0, s, c, d_bases_out, res.d); KCHK(); }
 	hipLaunchKernelGGL(k_kmer_correct, grid_waves(c.n_recs), dim3(WG), 0, s, c, w, k, canonical, t, R, d_bases_out, d_fixed, res.counters(), res.d); KCHK();
 	if (const int rc = res_home(h, res)) return rc;

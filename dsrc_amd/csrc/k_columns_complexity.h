@@ -1,12 +1,12 @@
 // Columnar complexity plan: the sixth planner -- poly-X runs cut off either end of the range, then a complexity filter (fastp's share
 // of positions that differ from their successor) and a windowed DUST score on what is left (include/dsrc_gpu.h:
 // dsrcgpu_columns_complexity_plan, where the rule stands as a serial loop).  Plan in, plan out, as k_adapt_plan; the check pass is
-// k_adapt_check.  The caller's input arrays are only read.  No counterpart in the reference.
+// k_col_plan_check.  The caller's input arrays are only read.  No counterpart in the reference.
 //
 // Portable subset only (__ballot, __shfl*, __popcll, __ffsll, vector atomics): tests/emu builds this file unchanged.
 #pragma once
 #include "k_common.h"
-#include "k_columns_adapt.h"
+#include "k_columns_common.h"
 
 #define CPLX_NONE 255u
 struct CplxRules { u32 tail, head, poly_min, poly_permille, min_len, min_cp, max_dust, max_dust_windows; };
@@ -15,7 +15,7 @@ enum { CPLX_KEPT = 0, CPLX_BASES, CPLX_CUT5, CPLX_CUT3, CPLX_HEAD_RECS, CPLX_TAI
 
 // The poly-X run at one end of the range x[0 .. n): its length (0: none of at least min_run positions) and its base in `which`.
 // Tiles of 64 positions are taken from that end inwards; lane l of a tile judges the position at distance k = base + l from the end
-// (from_end: x[n - 1 - k], else x[k]), so both ends are one loop.  The tile is three wave-uniform planes as in adapt_planes; for base X
+// (from_end: x[n - 1 - k], else x[k]), so both ends are one loop.  The tile is the three wave-uniform planes of col_planes; for base X
 // the match plane is a combination of them, and a lane's m is the carry of the tiles before plus one popcount of the plane below and at
 // its lane -- no scan.  The serial rule keeps the first position that reaches the highest score among those within the error budget:
 // per tile that is the highest score among the lanes that beat the running best (a wave maximum over the score's offset from the
@@ -31,9 +31,9 @@ __device__ __forceinline__ u64 cplx_poly_end(const u8* x, u64 n, u32 mask, bool 
 	{
 		const u64 k = base + lane;
 		const bool valid = k < n;
-		const u32 code = valid ? x[from_end ? n - 1 - k : k] : 0u;
 		const u64 in = __ballot(valid);
-		const u64 p0 = __ballot(valid && (code & 1u)), p1 = __ballot(valid && (code & 2u)), pn = __ballot(valid && code >= 4u);
+		u64 p0, p1, pn;
+		col_planes(x, n, base, from_end, p0, p1, pn);
 		const u64 upto = (2ull << lane) - 1ull;                // lanes 0 .. lane (lane 63: 2 << 63 is 0, minus 1 all ones)
 		const u64 L = k + 1;
 		const u64 seen = n - base > 64 ? base + 64 : n;
@@ -88,18 +88,13 @@ __device__ __forceinline__ u32 cplx_dust(u64 w0, u64 w1, u64 wn, u32 w)
 	return l >= 2 ? 10u * S / (l - 1u) : 0u;
 }
 
-// 64 positions from bit `sh` of the tile pair (cur, nxt); a shift by 64 is not a shift by 0
-__device__ __forceinline__ u64 cplx_funnel(u64 cur, u64 nxt, u32 sh) { return sh ? (cur >> sh) | (nxt << (64u - sh)) : cur; }
-
-// grid (gx), a wave per record with a grid stride, behind k_adapt_check as k_adapt_plan is: nothing happens unless that pass was
-// clean, and a record's offsets and range are tested again before its bytes are read.  The two ends are searched on the range as it
-// came (cplx_poly_end, only when that end's mask is set), then ONE pass over what is left serves both filters: a lane per position
-// holds the code itself, the next position's code comes by shuffle (lane 63: lane 0 of the next tile, which is loaded one tile
-// ahead, so each byte is loaded once), and the codes are compared as they are -- N equals N, 4 differs from 18.  The same tile
-// pair gives the DUST windows at bit offsets 0 and 32 and, once per record, the end-aligned one at a wave-uniform funnel shift.
-// A wave reads begin / end / keep of its record before lane 0 writes them (a ballot stands between the two), so each output array
-// may be its input counterpart.  Statistics: one to a lane, one vector atomic add per wave at the end, as in k_adapt_plan.
-__global__ void __launch_bounds__(WG) k_cplx_plan(ColIn c, AdaptPlanIn w, CplxRules R, u64* begin, u64* end, u8* keep, u32* info, u64* stats,
+// grid (gx), a wave per record with a grid stride, behind k_col_plan_check (k_columns_common.h: the re-check, in place, the
+// statistics).  The two ends are searched on the range as it came (cplx_poly_end, only when that end's mask is set), then ONE pass
+// over what is left serves both filters: a lane per position holds the code itself, the next position's code comes by shuffle (lane
+// 63: lane 0 of the next tile, which is loaded one tile ahead, so each byte is loaded once), and the codes are compared as they are
+// -- N equals N, 4 differs from 18.  The same tile pair gives the DUST windows at bit offsets 0 and 32 and, once per record, the
+// end-aligned one at a wave-uniform shift (col_funnel).
+__global__ void __launch_bounds__(WG) k_cplx_plan(ColIn c, ColPlanIn w, CplxRules R, u64* begin, u64* end, u8* keep, u32* info, u64* stats,
                                                   const u64* err)
 {
 	if (*err != COLE_NONE) return;
@@ -109,11 +104,9 @@ __global__ void __launch_bounds__(WG) k_cplx_plan(ColIn c, AdaptPlanIn w, CplxRu
 	u64 sum = 0;                                         // lane k adds up statistic k
 	for (u64 r = blockIdx.x * wpg + wave_id(); r < c.n_recs; r += gridDim.x * wpg)
 	{
-		const u64 s0 = c.seq_offs[r], s1 = c.seq_offs[r + 1];
-		if (s0 > s1 || s1 > c.bases_len) continue;
-		const u64 b = w.begin ? w.begin[r] : s0, e = w.begin ? w.end[r] : s1;
-		const bool keep_in = w.keep ? w.keep[r] != 0 : true;
-		if (b < s0 || e > s1 || b > e) continue;
+		u64 b, e;
+		bool keep_in;
+		if (!col_range(c, w, r, b, e, keep_in)) continue;
 		const u64 n = e - b;
 		u64 ob = b, oe = e;
 		bool keep_out = false;
@@ -131,20 +124,14 @@ __global__ void __launch_bounds__(WG) k_cplx_plan(ColIn c, AdaptPlanIn w, CplxRu
 			u32 dust = 0;
 			if (n2)
 			{
-				u32 cc = lane < n2 ? y[lane] : 0u;
-				u64 c0 = __ballot(lane < n2 && (cc & 1u)), c1 = __ballot(lane < n2 && (cc & 2u)), cn = __ballot(lane < n2 && cc >= 4u);
+				u64 c0, c1, cn;
+				u32 cc = col_planes(y, n2, 0, false, c0, c1, cn);
 				const u64 s_end = n2 >= 64 ? n2 - 64 : 0;           // the start of the end-aligned window
 				for (u64 base = 0; base < n2; base += 64)
 				{
 					u32 nc = 0;
 					u64 n0 = 0, n1 = 0, nn = 0;
-					if (n2 - base > 64)
-					{
-						const u64 j = base + 64 + lane;
-						const bool valid = j < n2;
-						nc = valid ? y[j] : 0u;
-						n0 = __ballot(valid && (nc & 1u)); n1 = __ballot(valid && (nc & 2u)); nn = __ballot(valid && nc >= 4u);
-					}
+					if (n2 - base > 64) nc = col_planes(y, n2, base + 64, false, n0, n1, nn);
 					const u32 down = __shfl_down(cc, 1), first = __shfl(nc, 0);
 					const u32 nb = lane == 63 ? first : down;
 					d += (u32)__popcll(__ballot(base + lane + 1 < n2 && cc != nb));
@@ -157,13 +144,13 @@ __global__ void __launch_bounds__(WG) k_cplx_plan(ColIn c, AdaptPlanIn w, CplxRu
 							if (base <= s_end) v = cplx_dust(c0, c1, cn, 64);
 							if (base + 32 <= s_end)
 							{
-								const u32 v2 = cplx_dust(cplx_funnel(c0, n0, 32), cplx_funnel(c1, n1, 32), cplx_funnel(cn, nn, 32), 64);
+								const u32 v2 = cplx_dust(col_funnel(c0, n0, 32), col_funnel(c1, n1, 32), col_funnel(cn, nn, 32), 64);
 								over += v2 > R.max_dust; dust = v2 > dust ? v2 : dust;
 							}
 							if ((s_end & 31u) && (s_end & ~63ull) == base)
 							{
 								const u32 sh = (u32)(s_end & 63u);
-								const u32 v3 = cplx_dust(cplx_funnel(c0, n0, sh), cplx_funnel(c1, n1, sh), cplx_funnel(cn, nn, sh), 64);
+								const u32 v3 = cplx_dust(col_funnel(c0, n0, sh), col_funnel(c1, n1, sh), col_funnel(cn, nn, sh), 64);
 								over += v3 > R.max_dust; dust = v3 > dust ? v3 : dust;
 							}
 						}
@@ -184,13 +171,12 @@ __global__ void __launch_bounds__(WG) k_cplx_plan(ColIn c, AdaptPlanIn w, CplxRu
 			               : (why && lane == why ? 1u : 0u);
 			sum += mine;
 		}
-		// in place: the wave meets once more, so that every lane has read begin / end / keep of this record before lane 0 overwrites them
-		const u64 met = __ballot(1);
+		const u64 met = __ballot(1);                         // in place: k_columns_common.h
 		if (lane == 0 && met)
 		{
 			begin[r] = ob; end[r] = oe; keep[r] = keep_out ? 1 : 0;
 			if (info) { info[2 * r] = i0; info[2 * r + 1] = i1; }
 		}
 	}
-	if (lane < CPLX_STATS && sum) atomicAdd((unsigned long long*)&stats[lane], (unsigned long long)sum);
+	col_stats_flush(stats, CPLX_STATS, sum);
 }

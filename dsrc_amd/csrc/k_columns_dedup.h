@@ -4,7 +4,7 @@
 // the considered records with one key exactly one is kept, its class's member of highest rank.  The caller's input arrays are only
 // read.  No counterpart in the reference.
 //
-// Three launches behind k_adapt_check of either side; each does nothing unless both error words are clean.
+// Three launches behind k_col_plan_check of either side; each does nothing unless both error words are clean.
 //   k_dedup_key      a wave per record: hash[r] and rank[r] into the arena
 //   k_dedup_insert   a wave per record: an open-addressed table of M = 2^m >= 2 * n_records slots, linear probing
 //   k_dedup_resolve  a lane per record: d_keep, d_dup_of, d_copies and the statistics
@@ -27,7 +27,7 @@
 // Portable subset only (__ballot, __shfl*, __popcll, vector atomics): tests/emu builds this file unchanged.
 #pragma once
 #include "k_common.h"
-#include "k_columns_adapt.h"
+#include "k_columns_common.h"
 
 #define DEDUP_EMPTY 0xFFFFFFFFu
 #define DEDUP_NOT_CONSIDERED (~0ull)
@@ -38,22 +38,18 @@ enum { DEDUP_CONSIDERED = 0, DEDUP_KEPT, DEDUP_DROPPED, DEDUP_MULTI, DEDUP_LARGE
 struct DedupIn
 {
 	ColIn c1, c2;
-	AdaptPlanIn w1, w2;
+	ColPlanIn w1, w2;
 	const u8* keep;
 	u64 key_bases, hash_mask;
 	u32 two, prefer;
 };
 struct DedupTable { u32* occ; u64* best; u32* count; u32* low; u64 mask; };       // mask = M - 1
 
-// the key range of record r on one side: x = c.bases + b, k bases.  false: offsets or range out of order (k_adapt_check has reported
-// it and nothing runs; tested again so that no byte outside the caller's arrays is ever read)
-__device__ __forceinline__ bool dedup_range(const ColIn& c, const AdaptPlanIn& w, u64 r, u64 key_bases, u64& b, u64& k)
+// the key range of record r on one side: x = c.bases + b, k bases.  false: offsets or range out of order (col_range)
+__device__ __forceinline__ bool dedup_range(const ColIn& c, const ColPlanIn& w, u64 r, u64 key_bases, u64& b, u64& k)
 {
-	const u64 s0 = c.seq_offs[r], s1 = c.seq_offs[r + 1];
-	if (s0 > s1 || s1 > c.bases_len) return false;
-	b = w.begin ? w.begin[r] : s0;
-	const u64 e = w.begin ? w.end[r] : s1;
-	if (b < s0 || e > s1 || b > e) return false;
+	u64 e;
+	if (!col_range(c, w, r, b, e)) return false;
 	const u64 n = e - b;
 	k = key_bases && n > key_bases ? key_bases : n;
 	return true;

@@ -9,22 +9,7 @@
 // the last one) and record r of that chunk starts at P(r) - P(f).  Positions are closed-form in the two offset arrays: no prefix pass.
 #pragma once
 #include "k_common.h"
-
-// the caller's arrays by value (the pointers of dsrcgpu_columns_in)
-struct ColIn
-{
-	const u8* bases; const u8* quals; const u8* titles;
-	const u64* seq_offs; const u64* title_offs;
-	u64 n_recs, bases_len, titles_len;
-	u32 plus_rep, qoff;
-};
-
-// the error word is (record << 4) | reason, COLE_NONE when clean: atomicMin keeps the lowest record and of that record the lowest reason
-enum { COLE_SEQ_ORDER = 0, COLE_SEQ_END, COLE_TITLE_ORDER, COLE_TITLE_END, COLE_TITLE_EMPTY, COLE_TITLE_AT, COLE_TITLE_NL, COLE_BASE, COLE_QUAL };
-#define COLE_NONE (~0ull)
-
-__device__ __forceinline__ u64 col_pos(const ColIn& c, u64 r, u64 s, u64 t) { return (1 + c.plus_rep) * t + 2 * s + (5 - c.plus_rep) * r; }
-__device__ __forceinline__ void col_err(u64* err, u64 r, u32 reason) { atomicMin((unsigned long long*)err, (unsigned long long)((r << 4) | reason)); }
+#include "k_columns_common.h"
 
 // ---- the check pass ------------------------------------------------------------------------------------------------------
 // grid (gx), a wave per record, lanes stride over the record's bytes.  A record's own four offsets are checked first (in order, closing

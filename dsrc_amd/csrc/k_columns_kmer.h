@@ -4,7 +4,7 @@
 // every window of a record: two orders of magnitude more inserts, nearly all of them hits on a key that is already there.  The
 // caller's input arrays are only read.  No counterpart in the reference.
 //
-//   k_kmer_windows   a lane per record, behind k_adapt_check: W (the windows of the call) and the three record statistics
+//   k_kmer_windows   a lane per record, behind k_col_plan_check: W (the windows of the call) and the three record statistics
 //   k_kmer_count     a wave per record, 64 windows a step: the table is filled
 //   k_kmer_header    one lane: the table's header is brought up to date, distinct / total come home with the statistics
 //   k_kmer_merge     a lane per slot of a source table: every (key, count) is added into another table
@@ -32,7 +32,7 @@
 // this file unchanged.
 #pragma once
 #include "k_common.h"
-#include "k_columns_adapt.h"
+#include "k_columns_common.h"
 #include "k_columns_dedup.h"
 
 #define KMER_EMPTY (~0ull)
@@ -52,12 +52,6 @@ __host__ __device__ __forceinline__ u64 kmer_header_word(u32 k, u32 canonical, u
 
 // by value: the table behind its header.  mask = M - 1; hash_mask cuts the hash to the table's hash_bits; limit = min(M, KMER_PROBE_LIMIT)
 struct KmerTab { u64* keys; u64* counts; u64 mask, hash_mask; u32 limit; };
-
-__device__ __forceinline__ u64 kmer_wave_sum(u64 v)
-{
-	for (u32 d = 32; d >= 1; d >>= 1) v += __shfl_xor(v, (int)d);
-	return v;
-}
 
 // bit j of v to bit 2j
 __device__ __forceinline__ u64 kmer_spread(u32 v)
@@ -131,43 +125,74 @@ __device__ __forceinline__ u64 kmer_find(const KmerTab& t, u64 key)
 	return 0;
 }
 
-// grid (gx), a lane per record with a grid stride, behind k_adapt_check (nothing unless that pass was clean; offsets and range are
-// tested again all the same).  stats[KMER_CONSIDERED .. KMER_WINDOWS]: lane s of a wave adds the wave's sum of statistic s.
-__global__ void __launch_bounds__(WG) k_kmer_windows(ColIn c, AdaptPlanIn w, u32 k, u64* stats, const u64* err)
+// ---- the window step ---------------------------------------------------------------------------------------------------------
+// What k_kmer_plan and k_kmer_correct do per 64 windows (k_kmer_count does the same and keeps its own text, see there).  The wave
+// holds 128 positions of the range as three wave-uniform bit planes each (col_planes): the step's own 64 (c0, c1, cn) and the 64
+// behind them (n0, n1, nn), which the next step takes over as its own, so every byte of the range is loaded once.  Lane i has the
+// window that starts at position base + i: it cuts 64 positions out of the planes (col_funnel) and no lane reads k bytes of its own
+// from HBM.  valid: the window exists; good: and holds no code above 3; key: kmer_key of its k bases (of no meaning unless good).  A
+// lane whose key equals the key of the good lane in front of it is not a head (head): equal neighbouring keys form a run, and only
+// its head walks the table.  b_valid, b_good, b_head: the ballots of the three.
+struct KmerStep { u64 key; bool valid, good, head; u64 b_valid, b_good, b_head; };
+
+__device__ __forceinline__ KmerStep kmer_step(u64 c0, u64 c1, u64 cn, u64 n0, u64 n1, u64 nn, u64 base, u64 n_win, u32 k, u64 kmask, u32 canonical)
+{
+	const u32 lane = lane_id();
+	KmerStep s;
+	const u64 w0 = col_funnel(c0, n0, lane), w1 = col_funnel(c1, n1, lane), wn = col_funnel(cn, nn, lane);
+	s.valid = base + lane < n_win;
+	s.good = s.valid && (wn & kmask) == 0;
+	const u64 m = kmer_spread((u32)(w0 & kmask)) | (kmer_spread((u32)(w1 & kmask)) << 1);
+	s.key = kmer_key(m, k, canonical);
+	const u64 prev = __shfl_up(s.key, 1);
+	s.b_valid = __ballot(s.valid); s.b_good = __ballot(s.good);
+	s.head = s.good && (lane == 0 || !((s.b_good >> (lane - 1u)) & 1ull) || prev != s.key);
+	s.b_head = __ballot(s.head);
+	return s;
+}
+
+// the count of every lane's key from a table that is only read: one kmer_find per head, and every lane takes the count of the head
+// of its run -- the highest head at or below the lane (a lane that is not good takes what it gets; its caller drops it)
+__device__ __forceinline__ u64 kmer_step_counts(const KmerTab& t, const KmerStep& s)
+{
+	const u32 lane = lane_id();
+	const u64 cnt = s.head ? kmer_find(t, s.key) : 0ull;
+	const u64 below = s.b_head & (lane == 63u ? ~0ull : (2ull << lane) - 1ull);
+	const int src = below ? 63 - __clzll((long long)below) : (int)lane;
+	return __shfl(cnt, src);
+}
+
+// grid (gx), a lane per record with a grid stride, behind k_col_plan_check.  stats[KMER_CONSIDERED .. KMER_WINDOWS]: lane s of a wave
+// adds the wave's sum of statistic s.
+__global__ void __launch_bounds__(WG) k_kmer_windows(ColIn c, ColPlanIn w, u32 k, u64* stats, const u64* err)
 {
 	if (*err != COLE_NONE) return;
 	u64 cons = 0, dropped = 0, shrt = 0, win = 0;
 	for (u64 r = (u64)blockIdx.x * blockDim.x + threadIdx.x; r < c.n_recs; r += (u64)gridDim.x * blockDim.x)
 	{
-		const u64 s0 = c.seq_offs[r], s1 = c.seq_offs[r + 1];
-		if (s0 > s1 || s1 > c.bases_len) continue;
-		const u64 b = w.begin ? w.begin[r] : s0, e = w.begin ? w.end[r] : s1;
-		if (b < s0 || e > s1 || b > e) continue;
+		u64 b, e;
+		if (!col_range(c, w, r, b, e)) continue;
 		if (w.keep && w.keep[r] == 0) { ++dropped; continue; }
 		++cons;
 		const u64 n = e - b;
 		if (n < k) ++shrt; else win += n - k + 1;
 	}
-	cons = kmer_wave_sum(cons); dropped = kmer_wave_sum(dropped); shrt = kmer_wave_sum(shrt); win = kmer_wave_sum(win);
+	cons = wave_sum64(cons); dropped = wave_sum64(dropped); shrt = wave_sum64(shrt); win = wave_sum64(win);
 	const u32 lane = lane_id();
 	const u64 mine = lane == KMER_CONSIDERED ? cons : lane == KMER_CAME_DROPPED ? dropped : lane == KMER_SHORT ? shrt : lane == KMER_WINDOWS ? win : 0ull;
 	if (mine) atomicAdd((unsigned long long*)&stats[lane], (unsigned long long)mine);
 }
 
-// grid (gx), a wave per record with a grid stride, 64 windows a step; lane i of a step has the window that starts at position
-// base + i of the range.
-// Staging: the wave holds 128 positions as three wave-uniform bit planes each (bit 0 of the code, bit 1, not-a-base; adapt_planes:
-// a byte per lane, 64 consecutive bytes per load instruction) -- the step's own 64 and the 64 behind them, which the NEXT step takes
-// over as its own.  Every byte of the range is loaded once; a lane cuts its window out of the planes with two shifts, and no lane
-// reads k bytes of its own from HBM.
-// Run aggregation: a lane whose key equals the key of the lane in front of it is not a head; a head adds the length of its run (up
-// to the next head or broken window, from two ballots) in ONE walk.  A homopolymer costs one atomic per step, not 64 on one word.
+// grid (gx), a wave per record with a grid stride, 64 windows a step.  The step is kmer_step's, spelled out here with the funnel in
+// its earlier form: with the shared text the kernel was shorter, and one leg of its timing lay above what the parent's runs allow.
+// Run aggregation: a head adds the length of its run (up to the next head or broken window, from two ballots) in ONE walk.  A
+// homopolymer costs one atomic per step, not 64 on one word.
 // Statistics: broken windows from ballots, counted / new / overflow per lane in registers; one wave sum each and one vector atomic
 // per statistic and wave at the end.  Integer sums: the order of the waves changes no bit of the table's content or the statistics.
 // AGG = false (every good window is a head of a run of one) and PLAIN = false are the measuring variants of a build with test hooks;
 // they give the same table.
 template <bool AGG, bool PLAIN>
-__global__ void __launch_bounds__(WG) k_kmer_count(ColIn c, AdaptPlanIn w, u32 k, u32 canonical, KmerTab t, u64* stats, const u64* err)
+__global__ void __launch_bounds__(WG) k_kmer_count(ColIn c, ColPlanIn w, u32 k, u32 canonical, KmerTab t, u64* stats, const u64* err)
 {
 	if (*err != COLE_NONE) return;
 	const u32 lane = lane_id();
@@ -186,11 +211,11 @@ __global__ void __launch_bounds__(WG) k_kmer_count(ColIn c, AdaptPlanIn w, u32 k
 		const u64 n_win = n - k + 1;
 		const u8* const x = c.bases + b;
 		u64 c0, c1, cn;
-		adapt_planes(x, n, 0, c0, c1, cn);
+		col_planes(x, n, 0, c0, c1, cn);
 		for (u64 base = 0; base < n_win; base += 64)
 		{
 			u64 n0 = 0, n1 = 0, nn = 0;
-			if (base + 64 < n) adapt_planes(x, n, base + 64, n0, n1, nn);
+			if (base + 64 < n) col_planes(x, n, base + 64, n0, n1, nn);
 			// 64 positions from base + lane on (lane 0 takes the planes as they are: a shift by 64 is not a shift by 0)
 			const u64 w0 = lane ? (c0 >> lane) | (n0 << (64u - lane)) : c0;
 			const u64 w1 = lane ? (c1 >> lane) | (n1 << (64u - lane)) : c1;
@@ -216,7 +241,7 @@ __global__ void __launch_bounds__(WG) k_kmer_count(ColIn c, AdaptPlanIn w, u32 k
 			c0 = n0; c1 = n1; cn = nn;
 		}
 	}
-	s_counted = kmer_wave_sum(s_counted); s_new = kmer_wave_sum(s_new); s_over = kmer_wave_sum(s_over);
+	s_counted = wave_sum64(s_counted); s_new = wave_sum64(s_new); s_over = wave_sum64(s_over);
 	const u64 mine = lane == KMER_COUNTED ? s_counted : lane == KMER_BROKEN ? s_broken : lane == KMER_NEW ? s_new : lane == KMER_OVERFLOW ? s_over : 0ull;
 	if (mine) atomicAdd((unsigned long long*)&stats[lane], (unsigned long long)mine);
 }
@@ -245,7 +270,7 @@ __global__ void __launch_bounds__(WG) k_kmer_merge(const u64* src_keys, const u6
 		if (kmer_insert(t, key, n, is_new)) { s_added += n; s_new += is_new ? 1u : 0u; }
 		else s_over += n;
 	}
-	s_keys = kmer_wave_sum(s_keys); s_new = kmer_wave_sum(s_new); s_added = kmer_wave_sum(s_added); s_over = kmer_wave_sum(s_over);
+	s_keys = wave_sum64(s_keys); s_new = wave_sum64(s_new); s_added = wave_sum64(s_added); s_over = wave_sum64(s_over);
 	const u32 lane = lane_id();
 	const u64 mine = lane == KMERGE_KEYS ? s_keys : lane == KMERGE_NEW ? s_new : lane == KMERGE_ADDED ? s_added : lane == KMERGE_OVERFLOW ? s_over : 0ull;
 	if (mine) atomicAdd((unsigned long long*)&stats[lane], (unsigned long long)mine);
@@ -278,7 +303,7 @@ __global__ void __launch_bounds__(WG) k_kmer_spectrum(const u64* keys, const u64
 		const u64 v = s_h[i];
 		if (v) atomicAdd((unsigned long long*)&hist[i], (unsigned long long)v);
 	}
-	distinct = kmer_wave_sum(distinct); total = kmer_wave_sum(total); single = kmer_wave_sum(single);
+	distinct = wave_sum64(distinct); total = wave_sum64(total); single = wave_sum64(single);
 	for (u32 d = 32; d >= 1; d >>= 1) { const u64 o = __shfl_xor(largest, (int)d); largest = largest > o ? largest : o; }
 	const u32 lane = lane_id();
 	if (lane == KSPEC_LARGEST) { if (largest) atomicMax((unsigned long long*)&totals[lane], (unsigned long long)largest); }
@@ -301,6 +326,6 @@ __global__ void __launch_bounds__(WG) k_kmer_lookup(KmerTab t, u32 k, u32 canoni
 		const u64 key = kmer_key(kmer_group_reverse(q, k), k, canonical);
 		out[i] = kmer_find(t, key);
 	}
-	bad = kmer_wave_sum(bad);
+	bad = wave_sum64(bad);
 	if (lane_id() == 0 && bad) atomicAdd((unsigned long long*)invalid, (unsigned long long)bad);
 }

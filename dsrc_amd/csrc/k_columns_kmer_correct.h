@@ -5,16 +5,15 @@
 // (include/dsrc_gpu.h: dsrcgpu_columns_kmer_correct has the rule as a serial loop).  Tadpole, Lighter, BFC, Musket and Quake do this;
 // the rule here is the conservative core of theirs.  No counterpart in the reference.
 //
-//   k_kmer_correct_copy   a lane per 8 bytes, behind k_adapt_check, out of place only: the bytes [S[0], S[n_records]) as they came
+//   k_kmer_correct_copy   a lane per 8 bytes, behind k_col_plan_check, out of place only: the bytes [S[0], S[n_records]) as they came
 //   k_kmer_correct        a wave per record, 64 windows a step: the runs, their verdicts, the repaired bytes, d_fixed
 //
-// The pass over the windows is k_kmer_plan<false>'s: the bases are staged through adapt_planes (every byte loaded once), a lane cuts
-// its window out of the planes, kmer_key gives the key, the head lane of a run of equal neighbouring keys walks with kmer_find and
-// the others take its count by shuffle.  New are the runs.  Per step the ballot of the valid windows that are not solid is scanned
-// with wave-uniform bit operations (first set bit, first clear bit behind it); a run that reaches bit 63 stays open and is carried
-// into the next step, a run that is still open behind the last step ends at the last window.  Only a run's two ends are kept, so a
-// read of 70 000 N is one run and costs nothing more than the plan's walk.
-// A closed run [w0, w1] with a position p (the rule's three placements) is resolved by the whole wave: one adapt_planes(x, n, w0)
+// The pass over the windows is k_kmer_plan<false>'s (kmer_step, kmer_step_counts): the head lane of a run of equal neighbouring keys
+// walks with kmer_find and the others take its count by shuffle.  New are the runs.  Per step the ballot of the valid windows that
+// are not solid is scanned with wave-uniform bit operations (first set bit, first clear bit behind it); a run that reaches bit 63
+// stays open and is carried into the next step, a run that is still open behind the last step ends at the last window.  Only a run's
+// two ends are kept, so a read of 70 000 N is one run and costs nothing more than the plan's walk.
+// A closed run [w0, w1] with a position p (the rule's three placements) is resolved by the whole wave: one col_planes(x, n, w0)
 // gives every position the run's windows need -- w0 .. w1 + k - 1, at most 2 k - 1 <= 61 of them --, lane j of a half-wave takes window
 // w0 + j with p's two plane bits replaced by a candidate; the two halves hold two candidates side by side, so four candidates are two
 // rounds of at most 31 walks each, and the verdict per candidate is one ballot against the mask of the run's length.  A second code
@@ -26,14 +25,13 @@
 // p'.  No other wave reads the record.  Out of place the loads go to the input and the stores to the output, which the copy kernel
 // has filled in an earlier launch.
 // Every branch around a ballot or a shuffle is wave-uniform; the walks are the only divergent code.  No LDS, no scratch memory.
-// Statistics: wave-uniform events, lane s keeps statistic s in a register and issues one vector atomic add at the wave's end.  Integer
-// sums: the result does not depend on the order of the waves.  Atomics touch the statistics words only, the table is never written,
-// and no lane waits for another wave.
+// Statistics: wave-uniform events, one to a lane (k_columns_common.h).  Atomics touch the statistics words only, the table is never
+// written, and no lane waits for another wave.
 //
 // Portable subset only (__ballot, __shfl*, __popcll, __ffsll, __clzll, vector atomics): tests/emu builds this file unchanged.
 #pragma once
 #include "k_common.h"
-#include "k_columns_adapt.h"
+#include "k_columns_common.h"
 #include "k_columns_kmer.h"
 
 enum { KCORR_CONSIDERED = 0, KCORR_CAME_DROPPED, KCORR_NO_WINDOW, KCORR_WINDOWS, KCORR_SOLID, KCORR_RUNS, KCORR_FIXED, KCORR_FIXED_N, KCORR_RECORDS_FIXED,
@@ -42,7 +40,7 @@ enum { KCORR_CONSIDERED = 0, KCORR_CAME_DROPPED, KCORR_NO_WINDOW, KCORR_WINDOWS,
 // by value in the kernel arguments
 struct KmerCorrectRules { u64 min_count; u32 max_quality; };
 
-// grid (gx), a lane per 8 bytes with a grid stride, behind k_adapt_check (nothing unless that pass was clean): out[S[0] .. S[n_recs]) =
+// grid (gx), a lane per 8 bytes with a grid stride, behind k_col_plan_check (nothing unless that pass was clean): out[S[0] .. S[n_recs]) =
 // bases[S[0] .. S[n_recs]), not a byte before or behind.  Words of 8 bytes where the two arrays sit alike in their words (the head
 // and the tail byte by byte), bytes throughout where they do not.
 __global__ void __launch_bounds__(WG) k_kmer_correct_copy(ColIn c, u8* out, const u64* err)
@@ -89,7 +87,7 @@ __device__ __forceinline__ u64 kcorr_run(const u8* x, const u8* q, u8* out_x, u6
 	if (why) return add + (lane == why ? 1u : 0u);
 	// the positions w0 .. w0 + 63 of the range; the run's windows need w0 .. w1 + k - 1 <= w0 + 60, and p - w0 <= k - 1
 	u64 r0, r1, rn;
-	adapt_planes(x, n, w0, r0, r1, rn);
+	col_planes(x, n, w0, r0, r1, rn);
 	const u32 at = (u32)(p - w0);
 	const u64 bit = 1ull << at;
 	const u32 orig = (rn & bit) ? 4u : (u32)((r0 >> at) & 1ull) | ((u32)((r1 >> at) & 1ull) << 1);
@@ -118,11 +116,11 @@ __device__ __forceinline__ u64 kcorr_run(const u8* x, const u8* q, u8* out_x, u6
 	return add + (lane == KCORR_FIXED || (lane == KCORR_FIXED_N && orig > 3u) ? 1u : 0u);
 }
 
-// grid (gx), a wave per record with a grid stride, 64 windows a step; lane i of a step has the window that starts at position base + i
-// of the range (staging and the cut of a window out of the planes: k_kmer_count).  out: addressed like c.bases; c.bases itself (in
-// place) or an array that k_kmer_correct_copy has filled.  See the head of this file for the runs and for why in place is sound.
-// fixed: n_recs entries or null; a record's entry is written whether or not it is considered.
-__global__ void __launch_bounds__(WG) k_kmer_correct(ColIn c, AdaptPlanIn w, u32 k, u32 canonical, KmerTab t, KmerCorrectRules R, u8* out, u64* fixed_out,
+// grid (gx), a wave per record with a grid stride, 64 windows a step; lane i of a step has the window that starts at position base +
+// i of the range (kmer_step).  out: addressed like c.bases; c.bases itself (in place) or an array that k_kmer_correct_copy has
+// filled.  See the head of this file for the runs and for why in place is sound.  fixed: n_recs entries or null; a record's entry is
+// written whether or not it is considered.
+__global__ void __launch_bounds__(WG) k_kmer_correct(ColIn c, ColPlanIn w, u32 k, u32 canonical, KmerTab t, KmerCorrectRules R, u8* out, u64* fixed_out,
                                                      u64* stats, const u64* err)
 {
 	if (*err != COLE_NONE) return;
@@ -132,11 +130,9 @@ __global__ void __launch_bounds__(WG) k_kmer_correct(ColIn c, AdaptPlanIn w, u32
 	u64 sum = 0;                                         // lane s adds up statistic s
 	for (u64 r = blockIdx.x * wpg + wave_id(); r < c.n_recs; r += gridDim.x * wpg)
 	{
-		const u64 s0 = c.seq_offs[r], s1 = c.seq_offs[r + 1];
-		if (s0 > s1 || s1 > c.bases_len) continue;
-		const u64 b = w.begin ? w.begin[r] : s0, e = w.begin ? w.end[r] : s1;
-		const bool keep_in = w.keep ? w.keep[r] != 0 : true;
-		if (b < s0 || e > s1 || b > e) continue;
+		u64 b, e;
+		bool keep_in;
+		if (!col_range(c, w, r, b, e, keep_in)) continue;
 		const u64 n = e - b;
 		const u64 n_win = keep_in && n >= k ? n - k + 1 : 0;
 		u64 fixed = 0;
@@ -148,30 +144,15 @@ __global__ void __launch_bounds__(WG) k_kmer_correct(ColIn c, AdaptPlanIn w, u32
 			u64 solid_n = 0, run_w0 = 0;
 			bool open = false;                               // a run that began at run_w0 has not ended yet
 			u64 c0, c1, cn;
-			adapt_planes(x, n, 0, c0, c1, cn);
+			col_planes(x, n, 0, c0, c1, cn);
 			for (u64 base = 0; base < n_win; base += 64)
 			{
 				u64 n0 = 0, n1 = 0, nn = 0;
-				if (base + 64 < n) adapt_planes(x, n, base + 64, n0, n1, nn);
-				// 64 positions from base + lane on (lane 0 takes the planes as they are: a shift by 64 is not a shift by 0)
-				const u64 v0 = lane ? (c0 >> lane) | (n0 << (64u - lane)) : c0;
-				const u64 v1 = lane ? (c1 >> lane) | (n1 << (64u - lane)) : c1;
-				const u64 vn = lane ? (cn >> lane) | (nn << (64u - lane)) : cn;
-				const bool valid = base + lane < n_win;
-				const bool good = valid && (vn & kmask) == 0;
-				const u64 m = kmer_spread((u32)(v0 & kmask)) | (kmer_spread((u32)(v1 & kmask)) << 1);
-				const u64 key = kmer_key(m, k, canonical);
-				const u64 prev = __shfl_up(key, 1);
-				const u64 b_valid = __ballot(valid), b_good = __ballot(good);
-				const bool head = good && (lane == 0 || !((b_good >> (lane - 1u)) & 1ull) || prev != key);
-				const u64 b_head = __ballot(head);
-				u64 cnt = head ? kmer_find(t, key) : 0ull;
-				// the head of this lane's run of equal keys: the highest head at or below the lane
-				const u64 below = b_head & (lane == 63u ? ~0ull : (2ull << lane) - 1ull);
-				const int src = below ? 63 - __clzll((long long)below) : (int)lane;
-				cnt = __shfl(cnt, src);
-				const u64 b_solid = __ballot(good && cnt >= R.min_count);
-				const u64 bad = b_valid & ~b_solid;
+				if (base + 64 < n) col_planes(x, n, base + 64, n0, n1, nn);
+				const KmerStep st = kmer_step(c0, c1, cn, n0, n1, nn, base, n_win, k, kmask, canonical);
+				const u64 cnt = kmer_step_counts(t, st);
+				const u64 b_solid = __ballot(st.good && cnt >= R.min_count);
+				const u64 bad = st.b_valid & ~b_solid;
 				solid_n += (u64)__popcll(b_solid);
 				// the runs of this step: `from` is the first bit that has not been looked at
 				u32 from = 0;
@@ -200,5 +181,5 @@ __global__ void __launch_bounds__(WG) k_kmer_correct(ColIn c, AdaptPlanIn w, u32
 		sum += keep_in ? (lane == KCORR_CONSIDERED || (lane == KCORR_NO_WINDOW && n_win == 0) ? 1u : 0u) : (lane == KCORR_CAME_DROPPED ? 1u : 0u);
 		if (lane == 0 && fixed_out) fixed_out[r] = fixed;
 	}
-	if (lane < KCORR_N_STATS && sum) atomicAdd((unsigned long long*)&stats[lane], (unsigned long long)sum);
+	col_stats_flush(stats, KCORR_N_STATS, sum);
 }

@@ -5,27 +5,26 @@
 // A contaminant screen (BBDuk) and an abundance trim (khmer) are the two uses.  The caller's input arrays and the table are only
 // read.  No counterpart in the reference.
 //
-//   k_kmer_plan_longest  a lane per record, behind k_adapt_check: the most windows any considered record has (the median's scratch)
+//   k_kmer_plan_longest  a lane per record, behind k_col_plan_check: the most windows any considered record has (the median's scratch)
 //   k_kmer_plan          a wave per record, 64 windows a step: the plan and the annotations
 //
-// The walk is k_kmer_count's: the bases are staged through adapt_planes (every byte loaded once), a lane cuts its window out of the
-// planes, kmer_key gives the key and kmer_find walks as the inserts did (hash_mask included).  Equal neighbouring keys form a run
-// whose head lane alone walks; the others take its count by shuffle -- a poly-G tail costs one walk per step.  The table is never
-// written and nothing here is an atomic on it: two calls, or a call and a lookup, may read one table at the same time.
+// The walk is k_kmer_count's (kmer_step), and kmer_find walks as the inserts did (hash_mask included).  Equal neighbouring keys form
+// a run whose head lane alone walks; the others take its count by shuffle (kmer_step_counts) -- a poly-G tail costs one walk per step.
+// The table is never written and nothing here is an atomic on it: two calls, or a call and a lookup, may read one table at the same
+// time.
 // The median (MEDIAN = true only): the wave keeps min(count, 65535) of its record's good windows, compacted in window order, in
 // KMER_PLAN_LDS_WINDOWS 16-bit words of LDS of its own; a record with more windows keeps them in the wave's slice of `spill` (HBM
 // scratch the host sized from the longest range of the call).  The element of rank good / 2 comes from a 16-round radix select,
 // most significant bit first: a round counts the stored values that agree with the bits chosen so far and have a 0 in the round's
 // bit -- a ballot and a popcount per 64 values.  Both stores are read back by the wave that wrote them only, behind a wave fence.
-// Statistics: wave-uniform sums, lane s keeps statistic s in a register and issues one vector atomic add at the wave's end.  Integer
-// sums: the result does not depend on the order of the waves.  No lane waits for another wave: the loops are the bounded walk, the
-// steps of a record and the select.
+// Statistics: wave-uniform sums, one to a lane (k_columns_common.h).  No lane waits for another wave: the loops are the bounded
+// walk, the steps of a record and the select.
 //
 // Portable subset only (static __shared__, __ballot, __shfl*, __popcll, __ffsll, __clzll, the wave fence of k_common.h, vector
 // atomics): tests/emu builds this file unchanged.
 #pragma once
 #include "k_common.h"
-#include "k_columns_adapt.h"
+#include "k_columns_common.h"
 #include "k_columns_kmer.h"
 
 #define KMER_PLAN_LDS_WINDOWS 1024u                        // 16-bit counts a wave keeps in LDS: 32 KiB for a workgroup of 16 waves
@@ -40,22 +39,20 @@ enum { KPLAN_TRIM_NONE = 0, KPLAN_TRIM_FIRST_MISS, KPLAN_TRIM_FIRST_HIT };
 struct KmerPlanRules { u64 min_count; u32 min_hits, max_hits, min_permille, max_permille, min_median, max_median, trim, min_len; };
 struct KmerPlanOut { u64* begin; u64* end; u8* keep; u64* good; u64* hits; u64* median; };
 
-// grid (gx), a lane per record with a grid stride, behind k_adapt_check: *longest = the most windows of a considered record
-__global__ void __launch_bounds__(WG) k_kmer_plan_longest(ColIn c, AdaptPlanIn w, u32 k, u64* longest, const u64* err)
+// grid (gx), a lane per record with a grid stride, behind k_col_plan_check: *longest = the most windows of a considered record
+__global__ void __launch_bounds__(WG) k_kmer_plan_longest(ColIn c, ColPlanIn w, u32 k, u64* longest, const u64* err)
 {
 	if (*err != COLE_NONE) return;
 	u64 most = 0;
 	for (u64 r = (u64)blockIdx.x * blockDim.x + threadIdx.x; r < c.n_recs; r += (u64)gridDim.x * blockDim.x)
 	{
-		const u64 s0 = c.seq_offs[r], s1 = c.seq_offs[r + 1];
-		if (s0 > s1 || s1 > c.bases_len) continue;
-		const u64 b = w.begin ? w.begin[r] : s0, e = w.begin ? w.end[r] : s1;
-		if (b < s0 || e > s1 || b > e) continue;
+		u64 b, e;
+		if (!col_range(c, w, r, b, e)) continue;
 		if (w.keep && w.keep[r] == 0) continue;
 		const u64 n = e - b;
 		if (n >= k && n - k + 1 > most) most = n - k + 1;
 	}
-	for (u32 d = 32; d >= 1; d >>= 1) { const u64 o = __shfl_xor(most, (int)d); most = most > o ? most : o; }
+	most = wave_max64(most);
 	if (lane_id() == 0 && most) atomicMax((unsigned long long*)longest, (unsigned long long)most);
 }
 
@@ -79,12 +76,11 @@ template <typename P> __device__ __forceinline__ u32 kplan_select(P cnt, u64 n, 
 }
 
 // grid (gx), a wave per record with a grid stride, 64 windows a step; lane i of a step has the window that starts at position base + i
-// of the range (staging and the cut of a window out of the planes: k_kmer_count).  A wave reads begin / end / keep of its record
-// before lane 0 writes them (ballots stand between the two), so each output array may be its input counterpart.  Every branch
-// around a ballot or a shuffle is wave-uniform; the walks of the head lanes are the only divergent code.
+// of the range (kmer_step).  Plan in, plan out, in place if the caller likes (k_columns_common.h).  Every branch around a ballot or
+// a shuffle is wave-uniform; the walks of the head lanes are the only divergent code.
 // spill: gridDim.x * (blockDim.x / 64) slices of spill_stride 16-bit words, one per wave (MEDIAN only, null if no record needs it).
 template <bool MEDIAN>
-__global__ void __launch_bounds__(WG) k_kmer_plan(ColIn c, AdaptPlanIn w, u32 k, u32 canonical, KmerTab t, KmerPlanRules R, KmerPlanOut o, u16* spill,
+__global__ void __launch_bounds__(WG) k_kmer_plan(ColIn c, ColPlanIn w, u32 k, u32 canonical, KmerTab t, KmerPlanRules R, KmerPlanOut o, u16* spill,
                                                   u64 spill_stride, u64* stats, const u64* err)
 {
 	if (*err != COLE_NONE) return;
@@ -97,11 +93,9 @@ __global__ void __launch_bounds__(WG) k_kmer_plan(ColIn c, AdaptPlanIn w, u32 k,
 	u64 sum = 0;                                         // lane s adds up statistic s
 	for (u64 r = blockIdx.x * wpg + wave_id(); r < c.n_recs; r += gridDim.x * wpg)
 	{
-		const u64 s0 = c.seq_offs[r], s1 = c.seq_offs[r + 1];
-		if (s0 > s1 || s1 > c.bases_len) continue;
-		const u64 b = w.begin ? w.begin[r] : s0, e = w.begin ? w.end[r] : s1;
-		const bool keep_in = w.keep ? w.keep[r] != 0 : true;
-		if (b < s0 || e > s1 || b > e) continue;
+		u64 b, e;
+		bool keep_in;
+		if (!col_range(c, w, r, b, e, keep_in)) continue;
 		const u64 n = e - b;
 		const u64 n_win = keep_in && n >= k ? n - k + 1 : 0;
 		u64 good_n = 0, hits = 0, first_miss = n_win, first_hit = n_win;
@@ -112,39 +106,24 @@ __global__ void __launch_bounds__(WG) k_kmer_plan(ColIn c, AdaptPlanIn w, u32 k,
 		{
 			const u8* const x = c.bases + b;
 			u64 c0, c1, cn;
-			adapt_planes(x, n, 0, c0, c1, cn);
+			col_planes(x, n, 0, c0, c1, cn);
 			for (u64 base = 0; base < n_win; base += 64)
 			{
 				u64 n0 = 0, n1 = 0, nn = 0;
-				if (base + 64 < n) adapt_planes(x, n, base + 64, n0, n1, nn);
-				// 64 positions from base + lane on (lane 0 takes the planes as they are: a shift by 64 is not a shift by 0)
-				const u64 w0 = lane ? (c0 >> lane) | (n0 << (64u - lane)) : c0;
-				const u64 w1 = lane ? (c1 >> lane) | (n1 << (64u - lane)) : c1;
-				const u64 wn = lane ? (cn >> lane) | (nn << (64u - lane)) : cn;
-				const bool valid = base + lane < n_win;
-				const bool good = valid && (wn & kmask) == 0;
-				const u64 m = kmer_spread((u32)(w0 & kmask)) | (kmer_spread((u32)(w1 & kmask)) << 1);
-				const u64 key = kmer_key(m, k, canonical);
-				const u64 prev = __shfl_up(key, 1);
-				const u64 b_valid = __ballot(valid), b_good = __ballot(good);
-				const bool head = good && (lane == 0 || !((b_good >> (lane - 1u)) & 1ull) || prev != key);
-				const u64 b_head = __ballot(head);
-				u64 cnt = head ? kmer_find(t, key) : 0ull;
-				// the head of this lane's run: the highest head at or below the lane (a lane that is not good takes what it gets and drops it)
-				const u64 below = b_head & (lane == 63u ? ~0ull : (2ull << lane) - 1ull);
-				const int src = below ? 63 - __clzll((long long)below) : (int)lane;
-				cnt = __shfl(cnt, src);
-				const bool hit = good && cnt >= R.min_count;
-				const u64 b_hit = __ballot(hit), b_miss = b_valid & ~b_hit;
+				if (base + 64 < n) col_planes(x, n, base + 64, n0, n1, nn);
+				const KmerStep st = kmer_step(c0, c1, cn, n0, n1, nn, base, n_win, k, kmask, canonical);
+				const u64 cnt = kmer_step_counts(t, st);
+				const bool hit = st.good && cnt >= R.min_count;
+				const u64 b_hit = __ballot(hit), b_miss = st.b_valid & ~b_hit;
 				if (first_hit == n_win && b_hit) first_hit = base + (u64)__ffsll((long long)b_hit) - 1ull;
 				if (first_miss == n_win && b_miss) first_miss = base + (u64)__ffsll((long long)b_miss) - 1ull;
-				if (stored && good)
+				if (stored && st.good)
 				{
-					const u64 at = good_n + (u64)__popcll(b_good & lanemask_lt());
+					const u64 at = good_n + (u64)__popcll(st.b_good & lanemask_lt());
 					const u16 v = (u16)(cnt < (u64)KMER_PLAN_COUNT_CAP ? cnt : (u64)KMER_PLAN_COUNT_CAP);
 					if (in_lds) my_lds[at] = v; else my_spill[at] = v;
 				}
-				good_n += (u64)__popcll(b_good); hits += (u64)__popcll(b_hit);
+				good_n += (u64)__popcll(st.b_good); hits += (u64)__popcll(b_hit);
 				c0 = n0; c1 = n1; cn = nn;
 			}
 		}
@@ -172,9 +151,7 @@ __global__ void __launch_bounds__(WG) k_kmer_plan(ColIn c, AdaptPlanIn w, u32 k,
 			sum += mine;
 		}
 		else if (lane == KPLAN_CAME_DROPPED) sum += 1;
-		// in place: the wave meets once more, so that every lane has read begin / end / keep of this record before lane 0 overwrites them
-		// (in lockstep that holds anyway; a record without a window has met nowhere else)
-		const u64 met = __ballot(1);
+		const u64 met = __ballot(1);                         // in place: k_columns_common.h
 		if (lane == 0 && met)
 		{
 			o.begin[r] = b; o.end[r] = keep_in ? e_out : e; o.keep[r] = keep_in && reason == 0 ? 1 : 0;
@@ -183,5 +160,5 @@ __global__ void __launch_bounds__(WG) k_kmer_plan(ColIn c, AdaptPlanIn w, u32 k,
 			if (o.median) o.median[r] = median;
 		}
 	}
-	if (lane < KPLAN_N_STATS && sum) atomicAdd((unsigned long long*)&stats[lane], (unsigned long long)sum);
+	col_stats_flush(stats, KPLAN_N_STATS, sum);
 }

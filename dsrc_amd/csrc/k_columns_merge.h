@@ -12,13 +12,15 @@
 // builds this file unchanged.
 #pragma once
 #include "k_common.h"
+#include "k_columns_common.h"
+#include "k_columns_sel.h"
 #include "k_columns_pair.h"
 
 #define MERGE_NOT (~0ull)
 #define MERGE_MAX_INSERT (1ull << 40)
 #define MERGE_STEPS 4u                                   // steps of 64 overlap positions the judge loads at once
 struct MergeRules { u32 min_overlap, max_mm, permille, qcap; };
-struct MergeWhat { AdaptPlanIn w1, w2; const u8* keep; const u64* insert; };
+struct MergeWhat { ColPlanIn w1, w2; const u8* keep; const u64* insert; };      // w<s>.keep is not used: ONE flag covers the pair
 enum { MERGE_MERGED = 0, MERGE_BASES, MERGE_OVERLAP, MERGE_AGREE, MERGE_CORRECTED, MERGE_ONE_SIDED, MERGE_NEITHER, MERGE_NOT_KEPT, MERGE_NO_INSERT,
        MERGE_GEOMETRY, MERGE_SHORT, MERGE_BUDGET, MERGE_N_STATS };
 
@@ -34,20 +36,19 @@ __device__ __forceinline__ u32 merge_comp(u32 c)
 // one pair's place in insert coordinates: read 1's range lies at [a1, z1), the reverse complement of read 2's at [a2, z2)
 struct MergeGeo { u64 b1, e2, a1, z1, a2, z2; };
 
-// The reasons 1 .. 4 for pair r, in the rule's order, behind the tests of the record's offsets and ranges (which never fail behind a
-// clean check pass; they are what keeps every read inside the caller's arrays whatever the arrays hold): 0 = goes on to the budget,
+// The reasons 1 .. 4 for pair r, in the rule's order, behind the re-check of either side (k_columns_common.h): 0 = goes on to the budget,
 // else the statistic the pair counts in; ~0u = an offset or range is out of order, the pair counts in nothing.  No base is read here.
 __device__ __forceinline__ u32 merge_geometry(const ColIn& c1, const ColIn& c2, const MergeWhat& w, u32 min_overlap, u64 r, MergeGeo& g)
 {
 	// (every load of the pair's figures is issued before the first test: the arrays hold an entry per pair, so the addresses are good
 	// whatever the entries are, and the wave waits for memory once instead of four times in a row)
 	const u64 s1 = c1.seq_offs[r], t1 = c1.seq_offs[r + 1], s2 = c2.seq_offs[r], t2 = c2.seq_offs[r + 1];
-	const u64 b1 = w.w1.begin ? w.w1.begin[r] : s1, e1 = w.w1.begin ? w.w1.end[r] : t1;
-	const u64 b2 = w.w2.begin ? w.w2.begin[r] : s2, e2 = w.w2.begin ? w.w2.end[r] : t2;
+	u64 b1, e1, b2, e2;
+	col_range_load(w.w1, r, s1, t1, b1, e1);
+	col_range_load(w.w2, r, s2, t2, b2, e2);
 	const bool kept = w.keep ? w.keep[r] != 0 : true;
 	const u64 I = w.insert[r];
-	if (s1 > t1 || t1 > c1.bases_len || s2 > t2 || t2 > c2.bases_len) return ~0u;
-	if (b1 < s1 || e1 > t1 || b1 > e1 || b2 < s2 || e2 > t2 || b2 > e2) return ~0u;
+	if (!col_range_ok(c1, s1, t1, b1, e1) || !col_range_ok(c2, s2, t2, b2, e2)) return ~0u;
 	if (!kept) return MERGE_NOT_KEPT;
 	if (I == PAIR_NO_INSERT) return MERGE_NO_INSERT;
 	const u64 f1 = b1 - s1, n1 = e1 - b1, f2 = b2 - s2, n2 = e2 - b2;      // each below 2^56: no sum of two wraps
@@ -58,7 +59,7 @@ __device__ __forceinline__ u32 merge_geometry(const ColIn& c1, const ColIn& c2, 
 	return 0;
 }
 
-// grid (gx), a wave per pair with a grid stride, behind k_adapt_check of either side (nothing happens unless both passes were clean).
+// grid (gx), a wave per pair with a grid stride, behind k_col_plan_check of either side (nothing happens unless both passes were clean).
 // The reasons 1 .. 4 come from merge_geometry; for the budget the wave walks the overlap 64 positions a step, a lane per position,
 // MERGE_STEPS steps to a round (a 150-base overlap is one round: one wait for memory) --
 // read 1 forwards from b1 + (lo - a1), read 2 backwards from e2 - 1 - (lo - a2), both contiguous -- and three ballots and popcounts

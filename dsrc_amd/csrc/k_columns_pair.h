@@ -8,7 +8,7 @@
 // Portable subset only (__ballot, __shfl*, __popcll, __ffsll, wave_fence, LDS, vector atomics): tests/emu builds this file unchanged.
 #pragma once
 #include "k_common.h"
-#include "k_columns_adapt.h"
+#include "k_columns_common.h"
 
 #define PAIR_MAX_BASES 1024u
 #define PAIR_WORDS (PAIR_MAX_BASES / 64u)
@@ -50,20 +50,18 @@ __device__ __forceinline__ u32 pair_len(u32 c, u32 n1, u32 n2)
 	return min_u32(n1, n2 - (c - n1 + 1u));
 }
 
-// grid (gx), a wave per pair with a grid stride, behind k_adapt_check of either side (nothing happens unless both passes were clean, and a
-// pair's offsets and ranges are tested again before a byte is read).  A pair that is searched -- both mates came in kept, both ranges
-// at most PAIR_MAX_BASES long -- is laid down as bit planes (x = read 1's range, y = the reverse complement of read 2's), the wave
-// meets, and the n1 + n2 - 1 candidates are judged 64 at a time in the rule's order: lane l of batch k has candidate c = 64 k + l.  One
-// side of a candidate is shifted (x for d >= 0, y for d < 0) and one is not; per word of the overlap the lane cuts a 64-bit window of the
-// shifted side out of two neighbouring LDS words (bit offset 0: the first word as it is -- a shift by 64 is not a shift by 0), compares
-// it with the aligned word of the other side under the mask of the positions that are left of L (64 and more: all ones), and adds up the
-// popcounts.  The word loop runs to the longest overlap of the batch, which is that of its first candidate or of its first read-through
-// candidate -- wave-uniform, as every branch here; a batch whose longest overlap is below min_overlap is skipped.  A ballot and __ffsll
-// give the first accepted candidate; behind a batch with a hit none is read.  In place: a wave reads the plans of its pair before lane 0
-// writes them, with a ballot between the two, so each output may be its input counterpart and keep may be either incoming keep.
-// Statistics: lane k adds up statistic k in a register, one vector atomic per lane and wave at the end if it is not 0 -- sums, so the
-// result does not depend on the order of the waves.
-__global__ void __launch_bounds__(WG) k_pair_plan(ColIn c1, ColIn c2, AdaptPlanIn w1, AdaptPlanIn w2, PairRules R, PairOut o, u64* stats, const u64* err)
+// grid (gx), a wave per pair with a grid stride, behind k_col_plan_check of either side (k_columns_common.h: the re-check -- here
+// every figure of the pair is loaded before the first test --, in place, the statistics).  A pair that is searched -- both mates came
+// in kept, both ranges at most PAIR_MAX_BASES long -- is laid down as bit planes (x = read 1's range, y = the reverse complement of
+// read 2's), the wave meets, and the n1 + n2 - 1 candidates are judged 64 at a time in the rule's order: lane l of batch k has
+// candidate c = 64 k + l.  One side of a candidate is shifted (x for d >= 0, y for d < 0) and one is not; per word of the overlap the
+// lane cuts a 64-bit window of the shifted side out of two neighbouring LDS words (bit offset 0: the first word as it is -- a shift
+// by 64 is not a shift by 0), compares it with the aligned word of the other side under the mask of the positions that are left of L
+// (64 and more: all ones), and adds up the popcounts.  The word loop runs to the longest overlap of the batch, which is that of its
+// first candidate or of its first read-through candidate -- wave-uniform, as every branch here; a batch whose longest overlap is
+// below min_overlap is skipped.  A ballot and __ffsll give the first accepted candidate; behind a batch with a hit none is read.  In
+// place: each output may be its input counterpart, and keep may be either incoming keep.
+__global__ void __launch_bounds__(WG) k_pair_plan(ColIn c1, ColIn c2, ColPlanIn w1, ColPlanIn w2, PairRules R, PairOut o, u64* stats, const u64* err)
 {
 	if (err[0] != COLE_NONE || err[1] != COLE_NONE) return;
 	__shared__ u64 s_planes[WG / 64][6 * PAIR_WORDS];
@@ -74,11 +72,11 @@ __global__ void __launch_bounds__(WG) k_pair_plan(ColIn c1, ColIn c2, AdaptPlanI
 	for (u64 r = blockIdx.x * wpg + wave_id(); r < c1.n_recs; r += gridDim.x * wpg)
 	{
 		const u64 s1 = c1.seq_offs[r], t1 = c1.seq_offs[r + 1], s2 = c2.seq_offs[r], t2 = c2.seq_offs[r + 1];
-		if (s1 > t1 || t1 > c1.bases_len || s2 > t2 || t2 > c2.bases_len) continue;
-		const u64 b1 = w1.begin ? w1.begin[r] : s1, e1 = w1.begin ? w1.end[r] : t1;
-		const u64 b2 = w2.begin ? w2.begin[r] : s2, e2 = w2.begin ? w2.end[r] : t2;
+		u64 b1, e1, b2, e2;
+		col_range_load(w1, r, s1, t1, b1, e1);
+		col_range_load(w2, r, s2, t2, b2, e2);
 		const bool k1 = w1.keep ? w1.keep[r] != 0 : true, k2 = w2.keep ? w2.keep[r] != 0 : true;
-		if (b1 < s1 || e1 > t1 || b1 > e1 || b2 < s2 || e2 > t2 || b2 > e2) continue;
+		if (!col_range_ok(c1, s1, t1, b1, e1) || !col_range_ok(c2, s2, t2, b2, e2)) continue;
 		const u64 n1 = e1 - b1, n2 = e2 - b2;
 		const bool both = k1 && k2;
 		const bool is_long = both && (n1 > PAIR_MAX_BASES || n2 > PAIR_MAX_BASES);
@@ -149,14 +147,12 @@ __global__ void __launch_bounds__(WG) k_pair_plan(ColIn c1, ColIn c2, AdaptPlanI
 		               : lane == PAIR_NARROWED ? (found && (len1 < n1 || len2 < n2) ? 1u : 0u) : lane == PAIR_DROP_MATE ? (k1 != k2 ? 1u : 0u)
 		               : lane == PAIR_DROP_LEN ? (both && !keep_out ? 1u : 0u) : lane == PAIR_LONG ? (is_long ? 1u : 0u) : lane == PAIR_INSERT_SUM ? (found ? insert : 0u) : 0u;
 		sum += mine;
-		// in place: the wave meets once more, so that every lane has read the plans of this pair before lane 0 overwrites them (in
-		// lockstep that holds anyway; a pair that was not searched has met nowhere else)
-		const u64 met = __ballot(1);
+		const u64 met = __ballot(1);                         // in place: k_columns_common.h
 		if (lane == 0 && met)
 		{
 			o.begin1[r] = b1; o.end1[r] = b1 + len1; o.begin2[r] = b2; o.end2[r] = b2 + len2; o.keep[r] = keep_out ? 1 : 0;
 			if (o.insert) o.insert[r] = insert;
 		}
 	}
-	if (lane < PAIR_N_STATS && sum) atomicAdd((unsigned long long*)&stats[lane], (unsigned long long)sum);
+	col_stats_flush(stats, PAIR_N_STATS, sum);
 }

@@ -7,7 +7,7 @@
 // unchanged; there __shared__ is a process-wide static, so the kernel zeroes its tables itself.
 #pragma once
 #include "k_common.h"
-#include "k_columns_adapt.h"
+#include "k_columns_common.h"
 
 #define PROF_MAX_CYCLES 1024u
 #define PROF_SMALL_CYCLES 256u                           // the table capacity of the second instantiation
@@ -18,19 +18,14 @@ enum { PROF_RECORDS = 0, PROF_BASES, PROF_Q20, PROF_Q30, PROF_QSUM, PROF_GC, PRO
 // beside 2 x 16 waves, the large one once)
 __host__ __device__ __forceinline__ u32 prof_max_grid(u32 n_cycles) { return n_cycles <= PROF_SMALL_CYCLES ? 512u : 256u; }
 
-__device__ __forceinline__ u64 prof_wave_sum(u64 v)
-{
-	for (u32 d = 32; d >= 1; d >>= 1) v += __shfl_xor(v, (int)d);
-	return v;
-}
 __device__ __forceinline__ void prof_add(u64* p, u64 v) { atomicAdd((unsigned long long*)p, (unsigned long long)v); }
 
-// grid (gx), a wave per record with a grid stride, behind k_adapt_check (nothing happens unless that pass was clean, and a record's
-// offsets and range are tested again before its bytes are read).  The workgroup keeps a whole profile of C cycles in LDS, in the
-// layout of the result and in 64-bit words throughout: no partial can wrap, whatever a record's length (one record of 2^32 bases
-// may fold into one cycle), and the flush at the end is one loop.  CAP is the capacity of that table in cycles; the host picks
-// the instantiation.  The second launch bound asks for the registers of 8 waves per SIMD (64) where the table leaves room for two
-// workgroups on a CU: left alone the compiler takes 65, which is 7 waves, which is one workgroup of 16.
+// grid (gx), a wave per record with a grid stride, behind k_col_plan_check (k_columns_common.h: the re-check).  The workgroup keeps a
+// whole profile of C cycles in LDS, in the layout of the result and in 64-bit words throughout: no partial can wrap, whatever a
+// record's length (one record of 2^32 bases may fold into one cycle), and the flush at the end is one loop.  CAP is the capacity of
+// that table in cycles; the host picks the instantiation.  The second launch bound asks for the registers of 8 waves per SIMD (64)
+// where the table leaves room for two workgroups on a CU: left alone the compiler takes 65, which is 7 waves, which is one workgroup
+// of 16.
 // Per tile of 64 positions a lane has one base and one quality.  Positions below C go to their own cycle: 64 lanes, 64 different
 // addresses of the two per-cycle tables.  Positions from C on all fold into cycle C - 1: they are counted per class with ballots
 // (the quality sum from the eight bit planes of q: sum = sum_b 2^b popcount(class & plane b)) in wave-uniform registers and are
@@ -39,7 +34,7 @@ __device__ __forceinline__ void prof_add(u64* p, u64 v) { atomicAdd((unsigned lo
 // record from lane 0; the eight totals are summed one to a lane over the wave's records and added once per wave.
 // Everything is an integer sum: the result does not depend on the order of the waves.
 template <u32 CAP>
-__global__ void __launch_bounds__(WG, CAP <= PROF_SMALL_CYCLES ? 8 : 4) k_prof(ColIn c, AdaptPlanIn w, u32 C, u64* prof, const u64* err)
+__global__ void __launch_bounds__(WG, CAP <= PROF_SMALL_CYCLES ? 8 : 4) k_prof(ColIn c, ColPlanIn w, u32 C, u64* prof, const u64* err)
 {
 	if (*err != COLE_NONE) return;
 	__shared__ u64 s_p[PROF_WORDS(CAP)];
@@ -54,10 +49,8 @@ __global__ void __launch_bounds__(WG, CAP <= PROF_SMALL_CYCLES ? 8 : 4) k_prof(C
 	const u64 wave = (u32)__builtin_amdgcn_readfirstlane((int)wave_id());      // (the compiler is told that a record's figures are wave-uniform)
 	for (u64 r = blockIdx.x * wpg + wave; r < c.n_recs; r += gridDim.x * wpg)
 	{
-		const u64 s0 = c.seq_offs[r], s1 = c.seq_offs[r + 1];
-		if (s0 > s1 || s1 > c.bases_len) continue;
-		const u64 b = w.begin ? w.begin[r] : s0, e = w.begin ? w.end[r] : s1;
-		if (b < s0 || e > s1 || b > e) continue;
+		u64 b, e;
+		if (!col_range(c, w, r, b, e)) continue;
 		if (w.keep && w.keep[r] == 0) continue;
 		const u64 n = e - b;
 		const u8* const x = c.bases + b; const u8* const qp = c.quals + b;
@@ -98,7 +91,7 @@ __global__ void __launch_bounds__(WG, CAP <= PROF_SMALL_CYCLES ? 8 : 4) k_prof(C
 			}
 		}
 		// a lane's share of the quality sum is below 2^32 while the record has at most 2^24 bases, and so is the sum of all of them
-		const u64 qs = n <= (1u << 24) ? (u64)wave_sum((u32)qs_lane) : prof_wave_sum(qs_lane);
+		const u64 qs = n <= (1u << 24) ? (u64)wave_sum((u32)qs_lane) : wave_sum64(qs_lane);
 		if (n > C)
 		{
 			const u64 cnt = lane == 0 ? fc[0] : lane == 1 ? fc[1] : lane == 2 ? fc[2] : lane == 3 ? fc[3] : fc[4];

@@ -7,26 +7,7 @@
 // another workgroup: the three prefix sums of the compaction are separate launches (tile sums, scan of the tile sums, apply).
 #pragma once
 #include "k_common.h"
-#include "k_columns_enc.h"
-
-// reasons of the select's own checks, behind those of k_columns_enc.h in the same error word
-enum { COLS_BEGIN_LOW = 9, COLS_END_HIGH, COLS_RANGE_ORDER };
-
-__device__ __forceinline__ u64 wave_incl_scan64(u64 v)
-{
-	const u32 l = lane_id();
-	for (u32 d = 1; d < 64; d <<= 1)
-	{
-		const u64 t = (u64)__shfl_up((unsigned long long)v, d);
-		if (l >= d) v += t;
-	}
-	return v;
-}
-__device__ __forceinline__ u64 wave_sum64(u64 v)
-{
-	for (u32 d = 32; d >= 1; d >>= 1) v += (u64)__shfl_xor((unsigned long long)v, (int)d);
-	return v;
-}
+#include "k_columns_common.h"
 
 // ---- the trim plan ---------------------------------------------------------------------------------------------------------
 struct TrimRules { u32 c5, c3, min_len, max_n, min_mq; };
