@@ -30,6 +30,7 @@ EXPORTS = [
     "dsrcgpu_columns_profile", "dsrcgpu_columns_merge_device", "dsrcgpu_columns_dedup_plan",
     "dsrcgpu_columns_kmer_count", "dsrcgpu_kmer_table_merge", "dsrcgpu_kmer_spectrum", "dsrcgpu_kmer_lookup",
     "dsrcgpu_columns_kmer_plan", "dsrcgpu_columns_kmer_correct", "dsrcgpu_columns_complexity_plan",
+    "dsrcgpu_columns_demux_plan", "dsrcgpu_columns_partition_device",
 ]
 
 # error codes of include/dsrc_gpu.h that callers tell apart (DsrcGpuError.code)
@@ -120,6 +121,47 @@ class ComplexityRules(C.Structure):
 COMPLEXITY_STATS = ("records_kept", "bases_kept", "bases_cut_5", "bases_cut_3", "records_head_cut", "records_tail_cut") + \
     tuple("tail_" + x for x in "ACGT") + tuple("head_" + x for x in "ACGT") + ("dropped_length", "dropped_complexity", "dropped_dust")
 COMPLEXITY_NONE = 255            # DSRCGPU_COMPLEXITY_NONE: the head / tail base of a record without a cut at that end
+
+
+class DemuxRules(C.Structure):
+    """dsrcgpu_demux_rules: DemuxRules(barcodes, slots, max_mismatches, slot_max_mismatches, min_delta, cut, keep_unassigned,
+    min_length).  `barcodes` is a list with one entry per sample, each a list of one or two barcodes (bytes / sequences of codes
+    0 .. 3), one per slot; `slots` a list of (source, offset) pairs, one per slot: source 0 = the reads themselves, 1 / 2 = an index
+    read set.  The slot lengths are those of sample 0; slot_max_mismatches None = no limit per slot.  The library is the one that
+    refuses figures out of range (shorter barcodes of later samples are padded with code 255, which it refuses)."""
+    _fields_ = [("n_samples", C.c_uint32), ("n_slots", C.c_uint32), ("slot_source", C.c_uint32 * 2), ("slot_offset", C.c_uint32 * 2),
+                ("slot_len", C.c_uint32 * 2), ("slot_max_mismatches", C.c_uint32 * 2), ("max_mismatches", C.c_uint32), ("min_delta", C.c_uint32),
+                ("cut", C.c_uint32), ("keep_unassigned", C.c_uint32), ("min_length", C.c_uint32), ("barcodes", C.c_void_p),
+                ("reserved", C.c_uint32 * 3)]
+
+    def __init__(self, barcodes=(), slots=((0, 0),), max_mismatches=1, slot_max_mismatches=None, min_delta=1, cut=1, keep_unassigned=0,
+                 min_length=1, reserved=(0, 0, 0)):
+        super().__init__()
+        samples = [[bytes(bytearray(b)) for b in sample] for sample in barcodes]
+        self.n_samples, self.n_slots = len(samples), len(slots)
+        lens = [len(b) for b in samples[0][:2]] if samples else []
+        for s, (source, offset) in enumerate(list(slots)[:2]):
+            self.slot_source[s], self.slot_offset[s] = source, offset
+            self.slot_len[s] = lens[s] if s < len(lens) else 0
+            self.slot_max_mismatches[s] = DEMUX_NO_LIMIT if slot_max_mismatches is None else slot_max_mismatches[s]
+        packed = bytearray()
+        for sample in samples:
+            for s, n in enumerate(lens):
+                b = sample[s] if s < len(sample) else b""
+                packed += (b + b"\xff" * n)[:n]
+        self._codes = (C.c_uint8 * max(len(packed), 1))(*packed)          # (kept alive with the rules)
+        self.barcodes = C.cast(self._codes, C.c_void_p)
+        self.max_mismatches, self.min_delta, self.cut, self.keep_unassigned, self.min_length = max_mismatches, min_delta, cut, keep_unassigned, min_length
+        self.reserved = (C.c_uint32 * 3)(*reserved)
+
+
+DEMUX_MAX_SAMPLES = 1023         # DSRCGPU_DEMUX_MAX_SAMPLES
+DEMUX_MAX_BARCODE = 64           # DSRCGPU_DEMUX_MAX_BARCODE
+DEMUX_NO_LIMIT = 0xFFFFFFFF      # DSRCGPU_DEMUX_NO_LIMIT
+DEMUX_STATS = ("records_kept", "bases_kept", "bases_cut", "records_assigned", "assigned_perfect", "unassigned_short", "unassigned_no_match",
+               "unassigned_ambiguous", "dropped_length")
+DEMUX_REASONS = ("assigned", "short", "no_match", "ambiguous")
+PARTITION_MAX_CLASSES = 1024
 
 
 class PairRules(C.Structure):
@@ -612,6 +654,41 @@ class Handle:
                                                          C.c_void_p(d_keep_in), C.c_void_p(d_begin), C.c_void_p(d_end), C.c_void_p(d_keep),
                                                          C.c_void_p(d_info), stats))
         return list(stats)
+
+    def columns_demux_plan(self, cols_in: ColumnsIn, index_sets, rules: DemuxRules, d_begin_in, d_end_in, d_keep_in, d_begin: int, d_end: int,
+                           d_keep: int, d_class: int, d_info=None, d_class_counts=None):
+        """dsrcgpu_columns_demux_plan: every record of `cols_in` gets the sample whose barcodes lie nearest, read from the record under
+        the plan d_begin_in / d_end_in / d_keep_in (device addresses or None: whole reads, every record) or from `index_sets` (a list
+        of up to two ColumnsIn of equally many records).  Out: d_begin / d_end (uint64 each), d_keep (uint8), d_class (uint32: the
+        sample, n_samples for unassigned, 0xFFFFFFFF for a record that came in dropped) and, if wanted, d_info (uint32: best | second
+        << 8 | reason << 16) and d_class_counts (uint64, n_samples + 1, added to), device memory; an output may be the very array of
+        its input.  Returns the nine statistics (DEMUX_STATS names them)."""
+        stats = (C.c_uint64 * 9)()
+        index_sets = list(index_sets or ())
+        sets = (C.POINTER(ColumnsIn) * max(len(index_sets), 1))(*[C.pointer(s) for s in index_sets])
+        self._chk(self.L.dsrcgpu_columns_demux_plan(self.h, C.byref(cols_in), sets if index_sets else None, C.c_uint32(len(index_sets)),
+                                                    C.byref(rules), C.c_void_p(d_begin_in), C.c_void_p(d_end_in), C.c_void_p(d_keep_in),
+                                                    C.c_void_p(d_begin), C.c_void_p(d_end), C.c_void_p(d_keep), C.c_void_p(d_class),
+                                                    C.c_void_p(d_info), C.c_void_p(d_class_counts), stats))
+        return list(stats)
+
+    def columns_partition_device(self, cols_in: ColumnsIn, d_begin, d_end, d_keep, d_class, n_classes: int, out: Columns, d_source=None):
+        """dsrcgpu_columns_partition_device: the kept records of `cols_in` with d_class[r] < n_classes, cut to [begin, end), grouped by
+        class and in input order inside a class, into the device arrays `out`.  Returns (totals, class_records): totals = records,
+        bases, title bytes that come out and the kept records left out for their class; class_records = the exclusive prefix of the
+        records per class (n_classes + 1 entries).  DsrcGpuError.code == E_CAPACITY when an array is too small -- `need` of the
+        exception then holds the first three totals, `class_records` the prefix."""
+        totals = (C.c_uint64 * 4)()
+        recs = (C.c_uint64 * (max(int(n_classes), 0) + 1))()
+        rc = self.L.dsrcgpu_columns_partition_device(self.h, C.byref(cols_in), C.c_void_p(d_begin), C.c_void_p(d_end), C.c_void_p(d_keep),
+                                                     C.c_void_p(d_class), C.c_uint32(n_classes), C.byref(out), C.c_void_p(d_source), recs, totals)
+        if rc < 0:
+            e = DsrcGpuError(rc, self.L.dsrcgpu_last_error(self.h).decode())
+            e.need = list(totals)[:3] if rc == E_CAPACITY else None
+            e.class_records = list(recs) if rc == E_CAPACITY else None
+            e.totals = list(totals)
+            raise e
+        return list(totals), list(recs)
 
     def columns_pair_plan(self, cols_in1: ColumnsIn, cols_in2: ColumnsIn, rules: PairRules, plan1_in, plan2_in, d_begin1: int, d_end1: int,
                           d_begin2: int, d_end2: int, d_keep: int, d_insert=None):

@@ -4,7 +4,8 @@
 (dsrcgpu_columns_kmer_correct), pair_plan
 (dsrcgpu_columns_pair_plan), dedup_plan (dsrcgpu_columns_dedup_plan), merge_pairs (dsrcgpu_columns_merge_device), select_columns
 (dsrcgpu_columns_select_device), filter_columns and, for paired-end data,
-filter_pairs, the report on either side of them, profile_columns (dsrcgpu_columns_profile), and the k-mer table of a plan, count_kmers
+filter_pairs, demux_plan and partition_columns (dsrcgpu_columns_demux_plan, dsrcgpu_columns_partition_device) with class_view and
+demux_columns, the report on either side of them, profile_columns (dsrcgpu_columns_profile), and the k-mer table of a plan, count_kmers
 and KmerTable (dsrcgpu_columns_kmer_count, dsrcgpu_kmer_table_merge, dsrcgpu_kmer_spectrum, dsrcgpu_kmer_lookup), include/dsrc_gpu.h.
 
 The blocks are already in device memory; the arrays are allocated by torch on the same device and filled by the library's
@@ -407,7 +408,7 @@ def profile_columns(handle: _lib.Handle, cols: RecordColumns, begin=None, end=No
 
 def filter_columns(handle: _lib.Handle, cols: RecordColumns, titles: bool = True, adapters=None, adapter_min_overlap: int = 3,
                    adapter_max_error_permille: int = 100, profile: bool = False, dedup: bool = False, dedup_key_bases: int = 0,
-                   dedup_prefer: str = "first", kmers=None, screen=None, correct=None, complexity=None, **rules):
+                   dedup_prefer: str = "first", kmers=None, screen=None, correct=None, complexity=None, demux=None, **rules):
     """trim_plan(**rules) and select_columns with its plan in sequence: -> (RecordColumns of the trimmed, kept records, stats).
     adapters (see adapter_plan): between the two, adapter_plan narrows the trim plan -- the quality trim first, the adapter second,
     the order of cutadapt and fastp -- with the same min_length; stats is then the trim plan's dict plus a key "adapter" that holds
@@ -430,7 +431,15 @@ def filter_columns(handle: _lib.Handle, cols: RecordColumns, titles: bool = True
     the trim plan, saw the bases as they came.
     complexity (a dict of complexity_plan keywords): behind the adapter plan and in front of correct, complexity_plan cuts poly-X ends
     and drops low-complexity reads, with the filter's min_length unless the dict gives one; stats gets "complexity", its dict, and
-    everything behind it sees the narrowed plan."""
+    everything behind it sees the narrowed plan.
+    demux (a dict of demux_plan keywords, its `barcodes` among them): directly behind the trim plan, demux_plan assigns every record its
+    sample and cuts the inline barcode, with the filter's min_length unless the dict gives one, so that every later plan sees the
+    cut; the filter then ends in partition_columns instead of select_columns: the records come out grouped by sample, block_records
+    is the class prefix over n_samples (+ 1 with keep_unassigned) classes and class_view hands out a sample.  stats gets "demux", the
+    plan's dict plus "class_records".  ValueError: an inline slot together with quality_5 (the 5' trim would eat the barcode), and
+    dedup=True together with demux (duplicates are per sample: dedup the views)."""
+    if demux is not None:
+        demux = _check_demux(demux, cols, rules.get("quality_5", 0), dedup)
     if adapters is not None:
         codes = _adapter_codes(adapters)
     if complexity is not None:
@@ -444,6 +453,11 @@ def filter_columns(handle: _lib.Handle, cols: RecordColumns, titles: bool = True
     if dedup:
         _check_dedup_args(dedup_key_bases, dedup_prefer)
     begin, end, keep, stats = trim_plan(handle, cols, **rules)
+    classes = None
+    if demux is not None:
+        begin, end, keep, classes, m_stats = demux_plan(handle, cols, begin=begin, end=end, keep=keep,
+                                                        **dict(dict(min_length=rules.get("min_length", 1)), **demux))
+        stats = dict(stats, demux=m_stats)
     if adapters is not None:
         begin, end, keep, a_stats = adapter_plan(handle, cols, codes, begin, end, keep, adapter_min_overlap, adapter_max_error_permille,
                                                  rules.get("min_length", 1))
@@ -467,6 +481,10 @@ def filter_columns(handle: _lib.Handle, cols: RecordColumns, titles: bool = True
         stats = dict(stats, profile_before=before, profile_after=profile_columns(handle, cols, begin, end, keep, n_cycles=before.n_cycles))
     if kmers is not None:
         stats = dict(stats, kmers_after=count_kmers(handle, cols, kmers, begin, end, keep)[0])
+    if classes is not None:
+        n_classes = stats["demux"]["class_counts"].numel() - (0 if demux.get("keep_unassigned", False) else 1)
+        parts = partition_columns(handle, cols, classes, n_classes, begin, end, keep, titles=titles)
+        return parts, dict(stats, demux=dict(stats["demux"], class_records=parts.block_records.tolist()))
     return select_columns(handle, cols, begin, end, keep, titles=titles), stats
 
 
@@ -629,7 +647,7 @@ def filter_pairs(handle: _lib.Handle, cols1: RecordColumns, cols2: RecordColumns
                  overlap: bool = True, pair_min_overlap: int = 30, pair_max_mismatches: int = 5, pair_max_error_permille: int = 200,
                  adapter_min_overlap: int = 3, adapter_max_error_permille: int = 100, profile: bool = False, merge: bool = False,
                  merge_quality_cap: int = 41, dedup: bool = False, dedup_key_bases: int = 0, dedup_prefer: str = "first", kmers=None, screen=None,
-                 correct=None, complexity=None, **rules):
+                 correct=None, complexity=None, demux=None, **rules):
     """filter_columns for paired-end data: per side trim_plan(**rules) and, if adapters<s> is given, adapter_plan; then pair_plan with
     the same min_length, which cuts read-through found from the overlap of the mates and decides per PAIR; then one select_columns per
     side with that side's ranges and the joint keep -> (out1, out2, stats), out1.n_records == out2.n_records always and record j of
@@ -656,7 +674,15 @@ def filter_pairs(handle: _lib.Handle, cols1: RecordColumns, cols2: RecordColumns
     repairs the bases; with k= ONE table of both mates under their plans is counted first.  stats["read1"]["correct"] and
     stats["read2"]["correct"] are its dicts; everything behind it sees the repaired bases, "profile_before" the bases as they came.
     complexity (as in filter_columns): per side, behind that side's adapter plan and in front of correct, the screen and the pair plan --
-    poly-G tails spoil the overlap search; stats["read1"]["complexity"] and stats["read2"]["complexity"] are its dicts."""
+    poly-G tails spoil the overlap search; stats["read1"]["complexity"] and stats["read2"]["complexity"] are its dicts.
+    demux (a dict of demux_plan keywords, its `barcodes` among them): directly behind the two trim plans, demux_plan runs ONCE with read 1
+    as its reads; slot sources are named "read1", "read2", "index1", "index2" (`index=` carries the index sets; a slot on read 2 makes
+    read 2 one more index set, so at most one other beside it).  Its keep is ANDed into both sides, so every later plan sees it; with
+    cut, a slot on read 2 advances begin2 of assigned pairs behind offset + length.  At the end out1, out2 and `merged` are each
+    partitioned by the class of their source pair instead of selected: block_records is the class prefix of each.  stats["demux"]
+    is the plan's dict plus "class_records", that of out1 and out2.  ValueError as in filter_columns."""
+    if demux is not None:
+        demux, read2_cut = _check_demux_pairs(demux, cols1, cols2, rules.get("quality_5", 0), dedup)
     if complexity is not None:
         _check_complexity(complexity)
     if dedup:
@@ -674,8 +700,18 @@ def filter_pairs(handle: _lib.Handle, cols1: RecordColumns, cols2: RecordColumns
         _check_int("merge_quality_cap", merge_quality_cap, 0, 255)
     plans, stats = [], {}
     codes1, codes2 = (_adapter_codes(a) if a is not None else None for a in (adapters1, adapters2))
-    for name, cols, codes in (("read1", cols1, codes1), ("read2", cols2, codes2)):
-        begin, end, keep, side = trim_plan(handle, cols, **rules)
+    trimmed = [trim_plan(handle, cols, **rules) for cols in (cols1, cols2)]
+    classes = None
+    if demux is not None:
+        (tb1, te1, tk1, side1), (tb2, te2, tk2, side2) = trimmed
+        tb1, te1, tk1, classes, m_stats = demux_plan(handle, cols1, begin=tb1, end=te1, keep=tk1, **dict(dict(min_length=rules.get("min_length", 1)), **demux))
+        n_classes = m_stats["class_counts"].numel() - (0 if demux.get("keep_unassigned", False) else 1)
+        if read2_cut:                                        # (assigned: the barcode fits read 2 as it was stored)
+            assigned = (classes >= 0) & (classes < m_stats["class_counts"].numel() - 1)
+            tb2 = torch.where(assigned, torch.minimum(torch.maximum(tb2, cols2.seq_offsets[:-1] + read2_cut), te2), tb2)
+        trimmed = [(tb1, te1, tk1, side1), (tb2, te2, tk2 & tk1, side2)]
+        stats["demux"] = m_stats
+    for (name, cols, codes), (begin, end, keep, side) in zip((("read1", cols1, codes1), ("read2", cols2, codes2)), trimmed):
         if codes is not None:
             begin, end, keep, a_stats = adapter_plan(handle, cols, codes, begin, end, keep, adapter_min_overlap, adapter_max_error_permille,
                                                      rules.get("min_length", 1))
@@ -702,8 +738,10 @@ def filter_pairs(handle: _lib.Handle, cols1: RecordColumns, cols2: RecordColumns
         stats["pair"] = p_stats
         if dedup:
             keep, stats["dedup"] = dedup_plan(handle, cols1, cols2, b1, e1, b2, e2, keep, dedup_key_bases, dedup_prefer)
-        merged, flag, stats["merge"] = merge_pairs(handle, cols1, cols2, b1, e1, b2, e2, keep, insert, pair_min_overlap, pair_max_mismatches,
-                                                   pair_max_error_permille, merge_quality_cap, titles=titles)
+        merged, flag, stats["merge"], m_source = merge_pairs(handle, cols1, cols2, b1, e1, b2, e2, keep, insert, pair_min_overlap, pair_max_mismatches,
+                                                             pair_max_error_permille, merge_quality_cap, titles=titles, return_source=True)
+        if classes is not None:
+            merged = partition_columns(handle, merged, classes[m_source], n_classes, titles=titles)
         keep = keep & (flag ^ 1)                             # both hold 0 / 1
     elif overlap:
         b1, e1, b2, e2, keep, p_stats = pair_plan(handle, cols1, cols2, plans[0], plans[1], pair_min_overlap, pair_max_mismatches,
@@ -721,8 +759,13 @@ def filter_pairs(handle: _lib.Handle, cols1: RecordColumns, cols2: RecordColumns
     if kmers is not None:
         table, _ = count_kmers(handle, cols1, kmers, b1, e1, keep)
         stats["kmers_after"], _ = count_kmers(handle, cols2, kmers, b2, e2, keep, into=table)
-    out1 = select_columns(handle, cols1, b1, e1, keep, titles=titles)
-    out2 = select_columns(handle, cols2, b2, e2, keep, titles=titles)
+    if classes is not None:
+        out1 = partition_columns(handle, cols1, classes, n_classes, b1, e1, keep, titles=titles)
+        out2 = partition_columns(handle, cols2, classes, n_classes, b2, e2, keep, titles=titles)
+        stats["demux"] = dict(stats["demux"], class_records=out1.block_records.tolist())
+    else:
+        out1 = select_columns(handle, cols1, b1, e1, keep, titles=titles)
+        out2 = select_columns(handle, cols2, b2, e2, keep, titles=titles)
     return (out1, out2, merged, stats) if merge else (out1, out2, stats)
 
 
@@ -1065,3 +1108,252 @@ def _correct_step(handle, sides, correct):
             table, _ = count_kmers(handle, cols, correct["k"], begin, end, keep, into=table)
     kw = {key: v for key, v in correct.items() if key in ("min_count", "max_quality")}
     return [correct_kmers(handle, cols, table, begin, end, keep, **kw) for cols, begin, end, keep in sides]
+
+
+# ---- demultiplex (dsrcgpu_columns_demux_plan, dsrcgpu_columns_partition_device) --------------------------------------------------------
+_COMPLEMENT = {0: 3, 1: 2, 2: 1, 3: 0}
+_DEMUX_SOURCES = {"read": 0, "read1": 0, "index1": 1, "index2": 2}
+_DEMUX_KEYS = ("barcodes", "index", "slots", "max_mismatches", "slot_max_mismatches", "min_delta", "cut", "keep_unassigned", "min_length", "revcomp",
+               "counts")
+
+
+def _demux_barcodes(barcodes, revcomp=None):
+    """`barcodes` (one entry per sample: "ACGTAC", ("ACGTACGT", "TTGACCAA") or "ACGTACGT+TTGACCAA") -> a list of samples, each a list
+    of one or two bytes of codes 0 .. 3.  ValueError for characters outside ACGT, ragged lengths within a slot, samples of different
+    slot counts, duplicates and counts or lengths out of range."""
+    if isinstance(barcodes, (str, bytes, bytearray)) or not hasattr(barcodes, "__len__"):
+        raise ValueError("barcodes is a list with one barcode (a string over ACGT) or one pair of barcodes per sample")
+    if not 1 <= len(barcodes) <= _lib.DEMUX_MAX_SAMPLES:
+        raise ValueError("between 1 and %d samples are needed, %d given" % (_lib.DEMUX_MAX_SAMPLES, len(barcodes)))
+    samples = []
+    for entry in barcodes:
+        parts = entry.split("+") if isinstance(entry, str) else list(entry) if isinstance(entry, (tuple, list)) else None
+        if parts is None or not 1 <= len(parts) <= 2 or any(not isinstance(p, str) for p in parts):
+            raise ValueError("barcode %r is neither a string over ACGT nor a pair of them" % (entry,))
+        codes = []
+        for p in parts:
+            if any(ch not in _BASE_CODES for ch in p.upper()):
+                raise ValueError("barcode %r: only A, C, G and T are allowed" % (entry,))
+            if not 1 <= len(p) <= _lib.DEMUX_MAX_BARCODE:
+                raise ValueError("a barcode has 1 to %d bases, %r has %d" % (_lib.DEMUX_MAX_BARCODE, entry, len(p)))
+            codes.append([_BASE_CODES[ch] for ch in p.upper()])
+        samples.append(codes)
+    n_slots = len(samples[0])
+    if any(len(s) != n_slots for s in samples):
+        raise ValueError("every sample has the same number of barcodes")
+    for s in range(n_slots):
+        if any(len(sample[s]) != len(samples[0][s]) for sample in samples):
+            raise ValueError("the barcodes of slot %d have different lengths" % s)
+    if revcomp is not None:
+        flags = [revcomp] * n_slots if isinstance(revcomp, bool) else list(revcomp)
+        if len(flags) != n_slots or any(not isinstance(f, bool) for f in flags):
+            raise ValueError("revcomp is a bool per slot")
+        samples = [[[_COMPLEMENT[v] for v in reversed(b)] if f else b for b, f in zip(sample, flags)] for sample in samples]
+    samples = [[bytes(b) for b in sample] for sample in samples]
+    if len({tuple(sample) for sample in samples}) != len(samples):
+        raise ValueError("two samples have the same barcodes")
+    return samples
+
+
+def _demux_slots(slots, n_slots, n_index, lens, names=_DEMUX_SOURCES):
+    """`slots` (None, or per slot a (source, offset) pair; a source is 0 / "read", 1 / "index1", 2 / "index2") -> [(source, offset)]."""
+    if slots is None:
+        if n_index:
+            if n_index != n_slots:
+                raise ValueError("%d index read sets for barcodes of %d slots: say where each slot is read with slots=" % (n_index, n_slots))
+            return [(k + 1, 0) for k in range(n_slots)]
+        return [(0, sum(lens[:s])) for s in range(n_slots)]
+    slots = list(slots)
+    if len(slots) != n_slots:
+        raise ValueError("slots has one (source, offset) pair per barcode slot: %d needed, %d given" % (n_slots, len(slots)))
+    out = []
+    for slot in slots:
+        if not isinstance(slot, (tuple, list)) or len(slot) != 2:
+            raise ValueError("a slot is a (source, offset) pair, %r given" % (slot,))
+        source, offset = slot
+        source = names.get(source, source) if isinstance(source, str) else source
+        if not isinstance(source, int) or isinstance(source, bool) or not 0 <= source <= n_index:
+            raise ValueError("slot source %r: 0 or 'read' for the reads, 1 .. %d or 'index1' .. for the index read sets given" % (slot[0], n_index))
+        _check_int("slot offset", offset, 0, 0xFFFFFFFF - _lib.DEMUX_MAX_BARCODE)
+        out.append((source, offset))
+    return out
+
+
+def _check_demux_args(cols, barcodes, index=(), slots=None, max_mismatches=1, slot_max_mismatches=None, min_delta=1, cut=True, keep_unassigned=False,
+                      min_length=1, revcomp=None, counts=None):
+    """The keywords of demux_plan, checked -> (_lib.DemuxRules, samples, slots).  ValueError for anything out of range."""
+    samples = _demux_barcodes(barcodes, revcomp)
+    index = list(index or ())
+    if len(index) > 2 or any(not isinstance(x, RecordColumns) for x in index):
+        raise ValueError("index is a list of at most two RecordColumns")
+    if any(x.n_records != cols.n_records or x.bases.device != cols.bases.device for x in index):
+        raise ValueError("an index read set has one record per read, on the device of the columns")
+    lens = [len(b) for b in samples[0]]
+    slots = _demux_slots(slots, len(lens), len(index), lens)
+    _check_int("max_mismatches", max_mismatches, 0, sum(lens))
+    if slot_max_mismatches is not None:
+        slot_max_mismatches = list(slot_max_mismatches)
+        if len(slot_max_mismatches) != len(lens):
+            raise ValueError("slot_max_mismatches has one entry per barcode slot")
+        for v in slot_max_mismatches:
+            _check_int("slot_max_mismatches", v, 0, 0xFFFFFFFE)
+    _check_int("min_delta", min_delta, 0, 255)
+    _check_int("min_length", min_length, 0, 0xFFFFFFFF)
+    if counts is not None and (not isinstance(counts, torch.Tensor) or counts.dtype != torch.int64 or counts.numel() != len(samples) + 1 or
+                               counts.device != cols.bases.device or not counts.is_contiguous()):
+        raise ValueError("counts holds %d int64 counts on the device of the columns" % (len(samples) + 1))
+    rules = _lib.DemuxRules(samples, slots, max_mismatches, slot_max_mismatches, min_delta, int(bool(cut)), int(bool(keep_unassigned)), min_length)
+    return rules, samples, slots
+
+
+def demux_plan(handle: _lib.Handle, cols: RecordColumns, barcodes, begin=None, end=None, keep=None, index=(), slots=None, max_mismatches: int = 1,
+               slot_max_mismatches=None, min_delta: int = 1, cut: bool = True, keep_unassigned: bool = False, min_length: int = 1,
+               return_info: bool = False, counts=None, revcomp=None):
+    """dsrcgpu_columns_demux_plan on the records of `cols`: every record that came in kept (the plan begin / end / keep; None: whole
+    reads, every record) gets the sample whose barcodes lie nearest -> (begin, end, keep, classes, stats[, best, second, reason]) in
+    fresh tensors.  `barcodes` has one entry per sample: "ACGTAC", a pair ("ACGTACGT", "TTGACCAA") or "ACGTACGT+TTGACCAA"; the
+    barcodes of one slot have one length.  `slots` says where each slot is read, as (source, offset) pairs: source 0 / "read" = the
+    record's own range, 1 / "index1" and 2 / "index2" = the RecordColumns in `index` (record r of which belongs to read r), offset = the
+    bases in front of the barcode.  The default is inline at offset 0 (a second slot behind the first) when `index` is empty, else
+    one slot per index set at offset 0.  revcomp=(False, True) reverse-complements the barcodes of a slot on the host (i5 on some
+    instruments).  A record is assigned iff its best total distance is at most max_mismatches (and each slot's at most
+    slot_max_mismatches[s], None: no limit per slot) and the runner-up lies at least min_delta above it; cut=True moves an assigned
+    record's begin behind its inline barcodes; keep_unassigned=True keeps the others as class n_samples (bcl2fastq's
+    "Undetermined").  classes (int32) is the sample, n_samples for unassigned, -1 for a record that came in dropped; stats is a
+    dict with the keys of _lib.DEMUX_STATS plus "class_counts", the int64 tensor `counts` (n_samples + 1 entries, created as zeros
+    when None, ADDED to, so that the batches of a file sum).  best, second (int64; 255 = none) and reason (int64: index into
+    _lib.DEMUX_REASONS) are -1 for a record that came in dropped.  Duplicate barcodes, characters outside ACGT, ragged lengths within
+    a slot and arguments out of range raise ValueError before the library is called.  Nothing of the payload crosses to the host."""
+    rules, samples, _ = _check_demux_args(cols, barcodes, index, slots, max_mismatches, slot_max_mismatches, min_delta, cut, keep_unassigned,
+                                          min_length, revcomp, counts)
+    device = cols.bases.device
+    R = cols.n_records
+    plan, plan_held = _stage_plan(R, device, [(begin, end)], keep)
+    cin, held = _columns_in(cols, titles=False)
+    sets = [_columns_in(x, titles=False) for x in (index or ())]
+    i64 = dict(dtype=torch.int64, device=device)
+    out_begin = torch.empty(R, **i64); out_end = torch.empty(R, **i64)
+    out_keep = torch.empty(R, dtype=torch.uint8, device=device)
+    classes = torch.empty(R, dtype=torch.int32, device=device)
+    info = torch.empty(R, dtype=torch.int32, device=device) if return_info else None
+    if counts is None:
+        counts = torch.zeros(len(samples) + 1, **i64)
+    _quiesce(device)
+    stats = handle.columns_demux_plan(cin, [s[0] for s in sets], rules, *plan, _adr(out_begin), _adr(out_end), _adr(out_keep), _adr(classes),
+                                      _adr(info), counts.data_ptr())
+    del held, plan_held, sets
+    got = (out_begin, out_end, out_keep, classes, dict(dict(zip(_lib.DEMUX_STATS, stats)), class_counts=counts))
+    if not return_info:
+        return got
+    word = info.to(torch.int64)
+    dropped = word == -1
+    field = lambda v: torch.where(dropped, torch.full_like(v, -1), v)
+    return got + (field(word & 255), field((word >> 8) & 255), field((word >> 16) & 255))
+
+
+def partition_columns(handle: _lib.Handle, cols: RecordColumns, classes, n_classes: int, begin=None, end=None, keep=None, titles: bool = True,
+                      return_source: bool = False):
+    """dsrcgpu_columns_partition_device: select_columns that groups -- the records of `cols` with a non-zero `keep` entry (None: all)
+    and 0 <= classes[r] < n_classes come out class by class, in input order inside a class, cut to [begin[r], end[r]) (None: whole
+    reads) -> RecordColumns whose block_records is the class prefix (n_classes + 1 entries): class c is records block_records[c] ..
+    block_records[c + 1] - 1, class_view(parts, c) hands them out without a copy, and encode_columns(parts) writes one block per
+    non-empty class when given block_records without the repeats.  classes is an integer tensor with one entry per record, as
+    demux_plan returns it; return_source=True: -> (RecordColumns, source), source[j] = the index in `cols` of output record j.  The
+    order is the same on every run."""
+    _check_int("n_classes", n_classes, 1, _lib.PARTITION_MAX_CLASSES)
+    device = cols.bases.device
+    R = cols.n_records
+    _together((begin, end))
+    if not isinstance(classes, torch.Tensor) or classes.is_floating_point() or classes.numel() != R or classes.device != device:
+        raise ValueError("classes is an integer tensor with one entry per record, on the device of the columns")
+    classes = classes.to(torch.int32).contiguous()
+    cin, held = _columns_in(cols, titles)
+    plan, plan_held = _stage_plan(R, device, [(begin, end)], keep)
+    spare = held[-1]
+    d_class = classes.data_ptr() if R else spare.data_ptr()
+    _quiesce(device)
+    need = [0, 0, 0]
+    try:
+        handle.columns_partition_device(cin, *plan, d_class, n_classes, _lib.Columns(d_titles=spare.data_ptr() if titles else None))
+    except _lib.DsrcGpuError as e:
+        if e.code != _lib.E_CAPACITY:
+            raise
+        need = e.need
+    K, S, T = need
+    u8 = dict(dtype=torch.uint8, device=device); i64 = dict(dtype=torch.int64, device=device)
+    bases = torch.empty(S, **u8); quals = torch.empty(S, **u8)
+    seq_offsets = torch.empty(K + 1, **i64)
+    title_bytes = torch.empty(T if titles else 0, **u8)
+    title_offsets = torch.empty(K + 1 if titles else 0, **i64)
+    source = torch.empty(K, **i64)
+    ptr = lambda t: t.data_ptr() if t.numel() else spare.data_ptr()
+    out = _lib.Columns(ptr(bases), S, ptr(quals), S, ptr(title_bytes) if titles else None, T if titles else 0,
+                       seq_offsets.data_ptr(), title_offsets.data_ptr() if titles else None, K)
+    _quiesce(device)
+    totals, class_records = handle.columns_partition_device(cin, *plan, d_class, n_classes, out, _adr(source) if return_source else None)
+    assert totals[:3] == need
+    del held, plan_held
+    got = RecordColumns(bases, quals, title_bytes, seq_offsets, title_offsets, torch.tensor(class_records, **i64))
+    return (got, source) if return_source else got
+
+
+def class_view(parts: RecordColumns, c: int) -> RecordColumns:
+    """Class c of what partition_columns returned, without a copy: bases, quals and titles are shared, the two offset arrays are
+    slices (they do not start at 0, which every call here and encode_columns accept), block_records = [0, the class's records]."""
+    _check_int("c", c, 0, parts.block_records.numel() - 2)
+    lo, hi = (int(v) for v in parts.block_records[c: c + 2].tolist())
+    titled = parts.title_offsets.numel() == parts.n_records + 1
+    return RecordColumns(parts.bases, parts.quals, parts.titles, parts.seq_offsets[lo: hi + 1],
+                         parts.title_offsets[lo: hi + 1] if titled else parts.title_offsets,
+                         torch.tensor([0, hi - lo], dtype=torch.int64, device=parts.seq_offsets.device))
+
+
+def demux_columns(handle: _lib.Handle, cols: RecordColumns, barcodes, titles: bool = True, return_source: bool = False, **kw):
+    """demux_plan(**kw), then partition_columns with its plan and classes: -> (parts, stats[, source]).  parts.block_records is the
+    prefix over n_classes = n_samples + (1 if keep_unassigned else 0) classes, stats the plan's dict plus "class_records", that
+    prefix as a list."""
+    begin, end, keep, classes, stats = demux_plan(handle, cols, barcodes, **dict(kw, return_info=False))
+    n_classes = stats["class_counts"].numel() - (0 if kw.get("keep_unassigned", False) else 1)
+    got = partition_columns(handle, cols, classes, n_classes, begin, end, keep, titles=titles, return_source=return_source)
+    parts = got[0] if return_source else got
+    stats = dict(stats, class_records=parts.block_records.tolist())
+    return (parts, stats, got[1]) if return_source else (parts, stats)
+
+
+def _check_demux(demux, cols, quality_5, dedup, pairs=False):
+    """The `demux` dict of filter_columns / filter_pairs: the keywords of demux_plan, `barcodes` among them."""
+    if not isinstance(demux, dict) or "barcodes" not in demux or any(key not in _DEMUX_KEYS for key in demux):
+        raise ValueError("demux is a dict of demux_plan keywords (%s) that holds barcodes" % ", ".join(_DEMUX_KEYS))
+    if dedup:
+        raise ValueError("dedup=True together with demux: duplicates are per sample -- dedup the class views")
+    kw = dict(demux)
+    if pairs:
+        return kw
+    _, _, slots = _check_demux_args(cols, **kw)
+    if quality_5 and any(source == 0 for source, _ in slots):
+        raise ValueError("an inline barcode slot together with quality_5: the 5' trim would eat the barcode")
+    return kw
+
+
+def _check_demux_pairs(demux, cols1, cols2, quality_5, dedup):
+    """The `demux` dict of filter_pairs -> (the keywords for demux_plan on read 1, the advance of begin2 under cut or 0).  A slot on
+    "read2" turns read 2 into one more index set."""
+    kw = _check_demux(demux, cols1, quality_5, dedup, pairs=True)
+    index = list(kw.get("index", None) or ())
+    slots = kw.get("slots")
+    read2, n_index = [], len(index)
+    if slots is not None:
+        slots = [tuple(s) if isinstance(s, (tuple, list)) else s for s in slots]
+        if any(isinstance(s, tuple) and len(s) == 2 and s[0] == "read2" for s in slots):
+            if len(index) >= 2:
+                raise ValueError("a slot on read 2 takes the place of an index read set: at most one other beside it")
+            index = index + [cols2]
+            read2 = [i for i, s in enumerate(slots) if isinstance(s, tuple) and len(s) == 2 and s[0] == "read2"]
+            slots = [(len(index), s[1]) if i in read2 else s for i, s in enumerate(slots)]
+    kw = dict(kw, index=index, slots=slots)
+    _, samples, checked = _check_demux_args(cols1, **kw)
+    inline = any(source == 0 for source, _ in checked) or bool(read2)
+    if quality_5 and inline:
+        raise ValueError("an inline barcode slot together with quality_5: the 5' trim would eat the barcode")
+    advance = max([checked[i][1] + len(samples[0][i]) for i in read2], default=0)
+    return kw, advance if kw.get("cut", True) else 0

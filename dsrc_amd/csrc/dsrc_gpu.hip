@@ -57,6 +57,7 @@
 #include "k_columns_kmer_plan.h"
 #include "k_columns_kmer_correct.h"
 #include "k_columns_complexity.h"
+#include "k_columns_demux.h"
 
 namespace
 {

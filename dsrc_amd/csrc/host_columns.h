@@ -6,6 +6,7 @@
 // written (dsrcgpu_compress_columns_device, which hands its text to run_batch, is the one exception).  An entry point reads top to
 // bottom as: argument checks -> scratch -> launches -> results home -> report; what the calls share is in the helpers below.
 #pragma once
+#include <array>
 
 namespace
 {
@@ -874,6 +875,153 @@ int dsrcgpu_columns_kmer_correct(dsrcgpu_handle* h, const dsrcgpu_columns_in* in
 	hipLaunchKernelGGL(k_kmer_correct, grid_waves(c.n_recs), dim3(WG), 0, s, c, w, k, canonical, t, R, d_bases_out, d_fixed, res.counters(), res.d); KCHK();
 	if (const int rc = res_home(h, res)) return rc;
 	for (u32 i = 0; i < KCORR_N_STATS; ++i) stats[i] = res.home()[i];
+	return DSRCGPU_OK;
+}
+
+// the demultiplex plan (k_columns_demux.h): the rules are checked and every sample's barcodes packed into bit planes here (four words a
+// sample, uploaded to arena scratch), then the check pass of the adapter plan once per column set, each with an error word of its own
+// (`in` is reported first), and the planner; the error words and the statistics come home in one copy
+int dsrcgpu_columns_demux_plan(dsrcgpu_handle* h, const dsrcgpu_columns_in* in, const dsrcgpu_columns_in* const* index_sets, uint32_t n_index_sets,
+							   const dsrcgpu_demux_rules* rules, const uint64_t* d_begin_in, const uint64_t* d_end_in, const uint8_t* d_keep_in,
+							   uint64_t* d_begin, uint64_t* d_end, uint8_t* d_keep, uint32_t* d_class, uint32_t* d_info, uint64_t* d_class_counts,
+							   uint64_t stats[9])
+{
+	if (!h) return DSRCGPU_E_ARG;
+	if (!rules || !stats) return fail(h, DSRCGPU_E_ARG, "null argument");
+	for (u32 k = 0; k < DMX_STATS; ++k) stats[k] = 0;
+	ColIn c, ci[2] = {};
+	if (const int rc = col_in_args(h, in, 0, c)) return rc;
+	if (n_index_sets > 2) return fail(h, DSRCGPU_E_ARG, "demux: at most 2 index read sets");
+	if (n_index_sets && !index_sets) return fail(h, DSRCGPU_E_ARG, "null argument");
+	for (u32 k = 0; k < n_index_sets; ++k)
+	{
+		if (const int rc = col_in_args(h, index_sets[k], 0, ci[k])) return rc;
+		if (ci[k].n_recs != c.n_recs) return fail(h, DSRCGPU_E_ARG, "demux: %llu records of the reads, %llu of index set %u", (unsigned long long)c.n_recs, (unsigned long long)ci[k].n_recs, k + 1);
+	}
+	if (rules->n_samples < 1 || rules->n_samples > DSRCGPU_DEMUX_MAX_SAMPLES) return fail(h, DSRCGPU_E_ARG, "demux rules: n_samples must be 1 .. %u", (u32)DSRCGPU_DEMUX_MAX_SAMPLES);
+	if (rules->n_slots < 1 || rules->n_slots > 2) return fail(h, DSRCGPU_E_ARG, "demux rules: n_slots must be 1 or 2");
+	if (rules->cut > 1 || rules->keep_unassigned > 1) return fail(h, DSRCGPU_E_ARG, "demux rules: cut and keep_unassigned must be 0 or 1");
+	DemuxRules R{};
+	R.n_samples = rules->n_samples; R.n_slots = rules->n_slots; R.max_total = rules->max_mismatches; R.min_delta = rules->min_delta;
+	R.cut = rules->cut; R.keep_unassigned = rules->keep_unassigned; R.min_len = rules->min_length;
+	u32 all_len = 0;
+	for (u32 s = 0; s < 2; ++s)
+	{
+		if (s >= R.n_slots)
+		{
+			if (rules->slot_source[s] | rules->slot_offset[s] | rules->slot_len[s] | rules->slot_max_mismatches[s]) return fail(h, DSRCGPU_E_ARG, "demux rules: a figure of slot %u behind n_slots", s);
+			continue;
+		}
+		if (rules->slot_source[s] > n_index_sets) return fail(h, DSRCGPU_E_ARG, "demux rules: slot %u reads source %u, %u index read sets were given", s, rules->slot_source[s], n_index_sets);
+		if (rules->slot_len[s] < 1 || rules->slot_len[s] > DSRCGPU_DEMUX_MAX_BARCODE) return fail(h, DSRCGPU_E_ARG, "demux rules: slot %u: a length of 1 .. %u is needed", s, (u32)DSRCGPU_DEMUX_MAX_BARCODE);
+		R.src[s] = rules->slot_source[s]; R.off[s] = rules->slot_offset[s]; R.len[s] = rules->slot_len[s]; R.max_mm[s] = rules->slot_max_mismatches[s];
+		R.mask[s] = R.len[s] == 64 ? ~0ull : (1ull << R.len[s]) - 1ull;
+		all_len += R.len[s];
+		if (R.src[s] == 0)
+		{
+			if ((u64)R.off[s] + R.len[s] > 0xFFFFFFFFull) return fail(h, DSRCGPU_E_ARG, "demux rules: slot %u: offset + length above 2^32 - 1", s);
+			R.cut_len = std::max(R.cut_len, R.off[s] + R.len[s]);
+		}
+	}
+	if (rules->max_mismatches > all_len) return fail(h, DSRCGPU_E_ARG, "demux rules: max_mismatches above the summed barcode lengths");
+	if (!rules->barcodes) return fail(h, DSRCGPU_E_ARG, "null argument");
+	std::vector<u64> tab((size_t)4 * R.n_samples, 0);
+	for (u32 a = 0; a < R.n_samples; ++a)
+		for (u32 j = 0; j < all_len; ++j)
+		{
+			const u32 code = rules->barcodes[(size_t)a * all_len + j];
+			if (code > 3) return fail(h, DSRCGPU_E_ARG, "demux rules: sample %u: code %u at position %u (A C G T = 0 .. 3 only)", a, code, j);
+			const u32 s = j < R.len[0] ? 0 : 1, bit = s ? j - R.len[0] : j;
+			tab[4 * a + 2 * s] |= (u64)(code & 1u) << bit; tab[4 * a + 2 * s + 1] |= (u64)(code >> 1) << bit;
+		}
+	{	// two samples with the same barcodes in every slot: sorted copies side by side
+		std::vector<std::array<u64, 4>> keys(R.n_samples);
+		for (u32 a = 0; a < R.n_samples; ++a) keys[a] = {tab[4 * a], tab[4 * a + 1], tab[4 * a + 2], tab[4 * a + 3]};
+		std::sort(keys.begin(), keys.end());
+		if (std::adjacent_find(keys.begin(), keys.end()) != keys.end()) return fail(h, DSRCGPU_E_ARG, "demux rules: two samples have the same barcodes");
+	}
+	if (const int rc = reserved_clear(h, "demux rules", rules->reserved)) return rc;
+	if (const int rc = together(h, d_begin_in, d_end_in, "d_begin_in", "d_end_in")) return rc;
+	if (c.n_recs == 0) return DSRCGPU_OK;
+	if (!d_begin || !d_end || !d_keep || !d_class) return fail(h, DSRCGPU_E_ARG, "null argument");
+	HIPCHK(hipSetDevice(h->device));
+	hipStream_t s = h->stream;
+	if (const int rc = ensure_arena(h, (3 + DMX_STATS) * 8 + tab.size() * 8 + 1024)) return rc;
+	ResWords res = res_alloc(h, 3, DMX_STATS);            // an error word per column set, the nine statistics
+	u64* d_tab = AP<u64>(h, h->arena.alloc(tab.size() * 8));
+	if (const int rc = res_begin(h, res, "demux plan")) return rc;
+	HIPCHK(hipMemcpyAsync(d_tab, tab.data(), tab.size() * 8, hipMemcpyHostToDevice, s));
+	const ColPlanIn w{d_begin_in, d_end_in, d_keep_in}, whole{nullptr, nullptr, nullptr};
+	const DemuxSrc x1{ci[0].bases, ci[0].seq_offs, ci[0].bases_len}, x2{ci[1].bases, ci[1].seq_offs, ci[1].bases_len};
+	hipLaunchKernelGGL(k_col_plan_check, grid_threads(c.n_recs), dim3(WG), 0, s, c, w, res.d); KCHK();
+	for (u32 k = 0; k < n_index_sets; ++k) { hipLaunchKernelGGL(k_col_plan_check, grid_threads(c.n_recs), dim3(WG), 0, s, ci[k], whole, res.d + 1 + k); KCHK(); }
+	hipLaunchKernelGGL(k_demux_plan, grid_threads(c.n_recs, DMX_GRID), dim3(WG), 0, s, c, w, x1, x2, R, d_tab, d_begin, d_end, d_keep, d_class, d_info, d_class_counts,
+	                   res.counters(), res.d); KCHK();
+	if (const int rc = res_home(h, res, "dsrcgpu_columns_demux_plan")) return rc;
+	for (u32 k = 0; k < DMX_STATS; ++k) stats[k] = res.home()[k];
+	return DSRCGPU_OK;
+}
+
+// the partition (k_columns_demux.h): the count pass and the scan of its (class, tile) counts first -- the error word, the four totals
+// and the class prefix come home in one synchronisation, in front of the first kernel that writes the caller's arrays -- then the
+// rank pass gives the output order, the select's placement runs over it, and k_sel_gather moves the bytes
+int dsrcgpu_columns_partition_device(dsrcgpu_handle* h, const dsrcgpu_columns_in* in, const uint64_t* d_begin, const uint64_t* d_end, const uint8_t* d_keep,
+									 const uint32_t* d_class, uint32_t n_classes, const dsrcgpu_columns* out, uint64_t* d_source,
+									 uint64_t* class_records, uint64_t totals[4])
+{
+	if (!h) return DSRCGPU_E_ARG;
+	if (!out || !totals) return fail(h, DSRCGPU_E_ARG, "null argument");
+	totals[0] = totals[1] = totals[2] = totals[3] = 0;
+	if (n_classes < 1 || n_classes > DMX_MAX_CLASSES) return fail(h, DSRCGPU_E_ARG, "partition: n_classes must be 1 .. %u", (u32)DMX_MAX_CLASSES);
+	if (!class_records) return fail(h, DSRCGPU_E_ARG, "null argument");
+	for (u32 k = 0; k <= n_classes; ++k) class_records[k] = 0;
+	if (const int rc = together(h, d_begin, d_end, "d_begin", "d_end")) return rc;
+	if (!out->d_titles && out->titles_cap) return fail(h, DSRCGPU_E_ARG, "columns: titles_cap without d_titles");
+	const bool titles = out->d_titles != nullptr;
+	ColIn c;
+	if (const int rc = col_in_args(h, in, COL_QUALS | (titles ? COL_TITLES : 0), c)) return rc;
+	if (c.n_recs && !d_class) return fail(h, DSRCGPU_E_ARG, "null argument");
+	HIPCHK(hipSetDevice(h->device));
+	hipStream_t s = h->stream;
+	if (c.n_recs == 0) return nothing_out(h, out, titles);
+	const u64 n_tiles = (c.n_recs + WG - 1) / WG, n_counts = (u64)n_classes * n_tiles, n_chunks = (n_counts + WG - 1) / WG;
+	if (const int rc = ensure_arena(h, (size_t)(n_counts + n_chunks + n_classes + 3 * n_tiles + 2 * c.n_recs + 16) * 8 + 8 * 256 + 4096)) return rc;
+	ResWords res = res_alloc(h, 1, PART_TOTALS, 4);       // error word, the four totals, the scan's total and the placement's three
+	u64* d_counts = AP<u64>(h, h->arena.alloc((size_t)n_counts * 8));
+	u64* d_chunks = AP<u64>(h, h->arena.alloc((size_t)n_chunks * 8));
+	u64* d_crecs = AP<u64>(h, h->arena.alloc((size_t)(n_classes + 1) * 8));
+	u64* d_tiles = AP<u64>(h, h->arena.alloc((size_t)n_tiles * 24));
+	u64* d_order = AP<u64>(h, h->arena.alloc((size_t)c.n_recs * 8));
+	u64* d_pos = AP<u64>(h, h->arena.alloc((size_t)c.n_recs * 8));
+	if (const int rc = res_begin(h, res, "columns partition")) return rc;
+	const PartWhat p{SelWhat{d_begin, d_end, d_keep, titles ? 1u : 0u}, d_class, n_classes};
+	u64* const d_total = res.counters() + PART_TOTALS;
+	const u32 g_tiles = (u32)std::min<u64>(4096, n_tiles), g_chunks = (u32)std::min<u64>(4096, n_chunks);
+	hipLaunchKernelGGL(k_part_count, dim3(g_tiles), dim3(WG), 0, s, c, p, n_tiles, d_counts, res.counters(), res.d); KCHK();
+	hipLaunchKernelGGL(k_part_scan_sums, dim3(g_chunks), dim3(WG), 0, s, n_counts, d_counts, n_chunks, d_chunks); KCHK();
+	hipLaunchKernelGGL(k_part_scan_chunks, dim3(1), dim3(WG), 0, s, n_chunks, d_chunks, d_total); KCHK();
+	hipLaunchKernelGGL(k_part_scan_apply, dim3(g_chunks), dim3(WG), 0, s, n_counts, d_counts, n_chunks, d_chunks); KCHK();
+	hipLaunchKernelGGL(k_part_class_records, dim3(1), dim3(WG), 0, s, d_counts, n_tiles, n_classes, d_total, d_crecs); KCHK();
+	std::vector<u64> crecs((size_t)n_classes + 1);
+	HIPCHK(hipMemcpyAsync(crecs.data(), d_crecs, crecs.size() * 8, hipMemcpyDeviceToHost, s));
+	if (const int rc = res_home(h, res, nullptr, 1 + PART_TOTALS)) return rc;
+	const u64* const tot = res.home();
+	for (u32 k = 0; k < PART_TOTALS; ++k) totals[k] = tot[k];
+	for (u32 k = 0; k <= n_classes; ++k) class_records[k] = crecs[k];
+	if (const int rc = out_holds(h, out, titles, tot, "partition", "come out")) return rc;
+	if (tot[0] == 0) return nothing_out(h, out, titles);
+	SelOut o;
+	if (const int rc = out_arrays(h, out, titles, tot[1] != 0, d_source, tot, o)) return rc;
+	const u64 n_out = tot[0], n_otiles = (n_out + WG - 1) / WG;
+	const u32 g_otiles = (u32)std::min<u64>(4096, n_otiles);
+	HIPCHK(hipMemsetAsync(d_order, 0xFF, (size_t)n_out * 8, s));          // (no record)
+	HIPCHK(hipMemsetAsync(d_pos, 0xFF, (size_t)c.n_recs * 8, s));         // SEL_DROPPED
+	hipLaunchKernelGGL(k_part_rank, dim3(g_tiles), dim3(WG), 0, s, c, p, n_tiles, d_counts, n_out, d_order); KCHK();
+	hipLaunchKernelGGL(k_part_place_tiles, dim3(g_otiles), dim3(WG), 0, s, c, p, d_order, n_out, n_otiles, d_tiles); KCHK();
+	hipLaunchKernelGGL(k_sel_scan_tiles, dim3(1), dim3(WG), 0, s, n_otiles, d_tiles, d_total + 1); KCHK();
+	hipLaunchKernelGGL(k_part_place_apply, dim3(g_otiles), dim3(WG), 0, s, c, p, d_order, n_out, n_otiles, d_tiles, o, d_pos); KCHK();
+	hipLaunchKernelGGL(k_sel_gather, grid_waves(c.n_recs), dim3(WG), 0, s, c, p.w, o, d_pos); KCHK();
+	HIPCHK(hipStreamSynchronize(s));
 	return DSRCGPU_OK;
 }
 

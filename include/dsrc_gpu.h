@@ -362,6 +362,101 @@ int dsrcgpu_columns_complexity_plan(dsrcgpu_handle* h, const dsrcgpu_columns_in*
 		uint32_t* d_info                                                                 /* device, 2 per record, may be NULL */,
 		uint64_t stats[20]);
 
+/* dsrcgpu_columns_demux_plan: the seventh planner -- a sequencing run is a pool of samples, and every record gets the sample whose
+ * barcodes lie nearest (Hamming distance) to what the record holds at the barcode positions: inline at the front of the read, or in up
+ * to two index read sets (i7 / i5) of equally many records.  Plan in, plan out, plus a class per record for
+ * dsrcgpu_columns_partition_device to group by.  Conventions as dsrcgpu_columns_adapter_plan: the handle's own lane and stream, scratch
+ * from the arena, synchronised before it returns, codec state left alone, a colour-space handle: DSRCGPU_E_ARG.  Of every set only
+ * d_bases and d_seq_offs are read.  The plan in: d_begin_in / d_end_in (both NULL = whole reads, one without the other: DSRCGPU_E_ARG)
+ * and d_keep_in (NULL = every record; any non-zero byte keeps).  sources[0] is `in` under the plan, sources[k] is index_sets[k - 1].
+ * For record r that came in kept, with b = d_begin_in[r], e = d_end_in[r]:
+ *   for slot s: src = slot_source[s]
+ *     source 0:  lo = b + slot_offset[s],        limit = e
+ *     source k:  lo = S_k[r] + slot_offset[s],   limit = S_k[r + 1]      (S_k = that index set's d_seq_offs)
+ *     if lo + slot_len[s] > limit: SHORT                                  (the record is unassigned, reason "short"; no sample is compared)
+ *     x_s[j] = bases_src[lo + j]
+ *   for a = 0 .. n_samples - 1:
+ *     d_s = the number of j < slot_len[s] with x_s[j] != barcode[a][s][j]   (a read code >= 4 -- N .. 255 -- matches nothing)
+ *     D[a] = every d_s <= slot_max_mismatches[s] ? sum of d_s : 255
+ *   best = min D, at a* = the LOWEST index that holds it;  second = min of D[a] over a != a* (255 if there is none)
+ *   assigned iff best <= max_mismatches and second - best >= min_delta
+ *   not assigned: reason NO_MATCH if best > max_mismatches, else AMBIGUOUS
+ *   d_class[r] = assigned ? a* : n_samples
+ *   d_info[r]  = best | second << 8 | reason << 16        (reason 0 assigned, 1 short, 2 no match, 3 ambiguous; short: best = second = 255)
+ *   d_begin[r] = assigned && cut ? b + max over the source-0 slots of (slot_offset + slot_len) : b;     d_end[r] = e
+ *   d_keep[r]  = (assigned || keep_unassigned) && d_end[r] - d_begin[r] >= min_length
+ * A record that came in dropped is not compared: its range passes through, d_keep[r] = 0, d_class[r] = d_info[r] = 0xFFFFFFFF, and it
+ * counts nowhere.  Positions at or beyond e are outside the read whatever the array holds there.  d_info may be NULL.
+ * d_class_counts (device, n_samples + 1 entries, may be NULL): entry d_class[r] is incremented for every record that came in kept --
+ * ADDED to what the array holds, so that the batches of a file sum.
+ * Not done here: indels in the barcode, barcodes of different lengths within a slot, IUPAC wildcards, UMIs, quality-aware distances,
+ * barcodes at the 3' end of the range, a search for the barcode at more than one offset.
+ * stats (host): [0] records kept, [1] bases kept, [2] bases this call cut off kept records, [3] records assigned, [4] records assigned
+ * with best == 0, [5] unassigned short, [6] unassigned no match, [7] unassigned ambiguous, [8] records dropped for length (the flag rule
+ * passed, the length did not).
+ * n_records == 0: DSRCGPU_OK, stats 0.
+ * DSRCGPU_E_ARG, nothing written: n_samples 0 or above 1023; n_slots 0 or above 2; n_index_sets above 2; a slot source above
+ * n_index_sets; a slot length of 0 or above 64; a non-zero figure of a slot behind n_slots; cut or keep_unassigned above 1; a barcode
+ * code above 3; two samples whose barcodes are equal in every slot; max_mismatches above the summed lengths; a non-zero reserved
+ * field; a null d_begin, d_end, d_keep or d_class; one range end without the other; an index set whose n_records differs.
+ * DSRCGPU_E_INPUT ("dsrcgpu_columns_demux_plan, read N: columns: record ..." in dsrcgpu_last_error, N = 1: `in`, 2 / 3: an index set;
+ * outputs untouched), for kept and dropped records alike: d_seq_offs out of order or a closing entry above bases_len in any set, and
+ * for `in` d_begin_in[r] < S[r], d_end_in[r] > S[r + 1], d_begin_in[r] > d_end_in[r].  No input makes a kernel read outside the
+ * caller's arrays.
+ * In place: as dsrcgpu_columns_adapter_plan (d_begin == d_begin_in, d_end == d_end_in, d_keep == d_keep_in). */
+#define DSRCGPU_DEMUX_MAX_SAMPLES 1023
+#define DSRCGPU_DEMUX_MAX_BARCODE 64
+#define DSRCGPU_DEMUX_NO_LIMIT    0xFFFFFFFFu
+typedef struct dsrcgpu_demux_rules
+{
+	uint32_t n_samples;               /* 1 .. 1023 */
+	uint32_t n_slots;                 /* 1 .. 2: single or dual barcode */
+	uint32_t slot_source[2];          /* index into sources[]: 0 = `in` under the plan (inline barcode), 1.. = an index read set */
+	uint32_t slot_offset[2];          /* bases in front of the barcode: from the RANGE's begin (source 0), from the record's first base (others) */
+	uint32_t slot_len[2];             /* 1 .. 64 */
+	uint32_t slot_max_mismatches[2];  /* per slot; DSRCGPU_DEMUX_NO_LIMIT = only the total counts */
+	uint32_t max_mismatches;          /* of the total over the slots */
+	uint32_t min_delta;               /* the runner-up's total must lie at least this far above the best; 0: ties go to the lowest index */
+	uint32_t cut;                     /* 1: an ASSIGNED record's begin moves behind its inline barcodes */
+	uint32_t keep_unassigned;         /* 1: unassigned records stay kept, as class n_samples (bcl2fastq's "Undetermined") */
+	uint32_t min_length;
+	const uint8_t* barcodes;          /* host: sample a, slot s at barcodes + a * (len0 + len1) + (s ? len0 : 0); codes 0..3 */
+	uint32_t reserved[3];             /* must be 0 */
+} dsrcgpu_demux_rules;
+
+int dsrcgpu_columns_demux_plan(dsrcgpu_handle* h, const dsrcgpu_columns_in* in,
+		const dsrcgpu_columns_in* const* index_sets, uint32_t n_index_sets   /* 0..2; sources 1, 2; same n_records as `in` */,
+		const dsrcgpu_demux_rules* rules,
+		const uint64_t* d_begin_in, const uint64_t* d_end_in, const uint8_t* d_keep_in   /* device, may be NULL */,
+		uint64_t* d_begin, uint64_t* d_end, uint8_t* d_keep                              /* device, n_records each */,
+		uint32_t* d_class          /* device, n_records */,
+		uint32_t* d_info           /* device, n_records, may be NULL */,
+		uint64_t* d_class_counts   /* device, n_samples + 1, may be NULL; ADDED to, so the batches of a file sum */,
+		uint64_t stats[9]);
+
+/* dsrcgpu_columns_partition_device: the select that groups.  The records with a non-zero d_keep byte (NULL = all) and d_class[r] <
+ * n_classes come out CLASS-MAJOR -- class 0's records, then class 1's, and so on -- and inside a class in their input order; bases and
+ * qualities cut to [d_begin[r], d_end[r]) (both NULL = whole reads), titles whole, offsets from 0, the closing entries of
+ * out->d_seq_offs / out->d_title_offs written.  d_source (device, may be NULL): d_source[j] = the index in `in` of output record j.
+ * class_records (host, n_classes + 1 entries): the exclusive prefix of the records per class -- class c's records are output records
+ * class_records[c] .. class_records[c + 1] - 1, a slice of `out` (dsrcgpu_compress_columns_device takes d_seq_offs + k), so that
+ * every sample's archive comes out of one compaction.  totals (host): records, bases, title bytes that come out, and [3] the kept
+ * records left out because d_class[r] >= n_classes (a planner's unassigned class, when the caller does not want it).
+ * The order is computed, not raced for: the same input gives the same output, byte for byte, on every run.
+ * As dsrcgpu_columns_select_device: the capacities (any too small: DSRCGPU_E_CAPACITY, totals and class_records = what is needed, none
+ * of the caller's arrays written; a call with capacities of 0 sizes the arrays), out->d_titles == NULL with titles_cap 0 for "titles
+ * not wanted", DSRCGPU_E_INPUT for kept and dropped records alike, nothing kept or n_records == 0 (DSRCGPU_OK, totals 0, class_records
+ * all 0, offs[0] = 0), and the no-overlap rule, which covers d_class as an input.
+ * DSRCGPU_E_ARG: n_classes 0 or above 1024; a null d_class or class_records.
+ * Scratch: 8 bytes per (class, tile of one workgroup's records) and 16 per record, from the arena.
+ * Not done here: more than 1024 classes in one call (partition twice, by the high and the low half of the class). */
+int dsrcgpu_columns_partition_device(dsrcgpu_handle* h, const dsrcgpu_columns_in* in,
+		const uint64_t* d_begin, const uint64_t* d_end, const uint8_t* d_keep,
+		const uint32_t* d_class, uint32_t n_classes   /* 1 .. 1024 */,
+		const dsrcgpu_columns* out, uint64_t* d_source,
+		uint64_t* class_records   /* host, n_classes + 1: exclusive prefix of the records per class */,
+		uint64_t totals[4]        /* records, bases, title bytes that come out; kept records left out because d_class[r] >= n_classes */);
+
 /* dsrcgpu_columns_pair_plan: the third planner, for paired-end data -- two column sets of equally many records, record r of `in2` is
  * the mate of record r of `in1`.  It takes a plan in per side and gives a narrower plan out per side and ONE keep flag per pair, so
  * that two dsrcgpu_columns_select_device calls with that flag keep the two outputs in step.  Read-through is found from the pair
